@@ -4,6 +4,15 @@
     python bench.py [--gpus N] [--steps K] [--warmup W]          # plain shell: starts its own N workers
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N ...                                  # or under an external launcher
+    python bench.py ... --full                                    # + every secondary measurement (see below)
+    python bench.py ... --dump-outputs DIR                        # + DIR/mll.npy: the last timed step's MLL vector
+
+A plain run sets up, warms up, times K steps and prints the line (metric, value, unit, higher_is_better, dtype,
+ms_per_step, config, and the Cholesky roofline of the timed calls).  `--full` adds what takes work of its own: socket
+power over the timed steps, one instrumented step (per-kernel spans), HBM traffic (live rocprofv3 passes, or the
+committed profile of this build), the c4 region of a weak multi-GPU run, and with one GPU the Gram-kernel roofline, the
+other BASELINE configs, the probes, the vendor-Cholesky yardstick and the CPU baseline.  Inputs depend only on the
+arguments (fixed seeds), so `--dump-outputs` of two builds can be compared array for array.
 
 Launcher: without RANK/WORLD_SIZE in the environment this process never touches torch or the GPU; it starts
 N fresh worker processes (one per GPU, RANK/LOCAL_RANK/WORLD_SIZE/MASTER_* set) and relays rank 0's JSON line.
@@ -15,14 +24,14 @@ leaf traversal -> N x N Gram (+ jitter) -> blocked fp64 Cholesky -> triangular s
 path, the all-gather of the (B,) log-likelihoods over RCCL.  Inputs (X, y, packed forests, noise)
 are resident in HBM before the timed region; the output is the (B,) MLL vector on the device.
 The timed steps run the PRODUCTION path of the C ABI (no timing struct, no host synchronisation inside
-the library); the per-kernel breakdown comes from one separate instrumented step after the timed region.
+the library); with --full the per-kernel breakdown comes from one separate instrumented step after the timed region.
 
 Workload (BASELINE.json configs[2], SURVEY §8d "c3"): N=4096 points, d=8 continuous features,
 m=50 trees, B=256 forest samples PER GPU drawn from the BART depth prior (alpha .95, beta 2),
 noise_b ~ U[0.05,0.15), scale 1, MLL convention of examples/mcmc/mcmc_record_mll.py:57-74.
 Default = weak scaling (every rank evaluates its own 256 samples).  `--total B` = strong scaling: B samples
-in all, contiguous shards per rank (configs[3] "c4" is `--total 512 --gpus 8` = 64 per GPU); in weak mode
-with N > 1 the c4 split (512 / N per rank) is timed as a second region and reported under "c4_strong".
+in all, contiguous shards per rank (configs[3] "c4" is `--total 512 --gpus 8` = 64 per GPU); with --full, in weak
+mode with N > 1 the c4 split (512 / N per rank) is timed as a second region and reported under "c4_strong".
 """
 
 from __future__ import annotations
@@ -71,7 +80,18 @@ def parse(argv=None):
                     help="with --gpus > 1 and the nccl backend: an RCCL init / probe failure ends the run with a non-zero exit "
                          "(default).  --no-require-rccl lets the 8-byte-per-sample MLL gather fall back to gloo instead; "
                          "the JSON then says so (collective_backend != collective_backend_requested)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: power over the timed steps, the instrumented step (per-kernel spans), "
+                         "HBM traffic, the c4 region of a weak multi-GPU run, and with one GPU the Gram-kernel roofline, the other "
+                         "configs, the probes and the CPU baseline.  Without it a run sets up, warms up, times --steps steps and "
+                         "prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (the gathered (B,) MLL vector, float64) as "
+                         "DIR/mll.npy")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------
@@ -89,7 +109,8 @@ def launch(args) -> int:
         raise SystemExit("--gpus must be >= 1")
     port = _free_port()
     procs = []
-    live = n == 1 and args.live_traffic and not args.selftest_launcher and shutil.which("rocprofv3") is not None
+    live = (n == 1 and args.full and args.live_traffic and not args.selftest_launcher
+            and shutil.which("rocprofv3") is not None)
     line_file = None
     if live:  # rank 0 hands its JSON line to this process instead of printing it: see live_traffic()
         fd, line_file = tempfile.mkstemp(prefix="bark_bench_line_", suffix=".json")
@@ -511,7 +532,7 @@ class PowerSampler:
                 "source": "hwmon power1_input / freq1_input / power1_cap of this rank's card, sampled every 20 ms over the timed steps"}
 
 
-def timed_region(wl, steps, warmup, world, coll, gather):
+def timed_region(wl, steps, warmup, world, coll, gather, power_sampling=True):
     """W warm-up steps, then exactly K steps between barrier + synchronize fences; max over ranks."""
     import torch
 
@@ -527,7 +548,8 @@ def timed_region(wl, steps, warmup, world, coll, gather):
         out = gather(wl.run())
     fence()
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2 * steps)]
-    power = PowerSampler(wl.Xd.device.index)  # every rank samples its own card; rank 0's goes into the line
+    # every rank samples its own card; rank 0's goes into the line
+    power = PowerSampler(wl.Xd.device.index) if power_sampling else None
     if power:
         power.start()
     t0 = time.perf_counter()
@@ -613,7 +635,7 @@ def init_collective(world, rank, dev_index, requested, must_be_rccl):
 def selftest_worker(args, world, rank):
     """Launcher / rendezvous / collective set-up (incl. the RCCL-unavailable branch: BARK_BENCH_BACKEND=nccl on a box
     without GPUs) / gather / timing protocol on CPU: everything a worker does around the GPU work, for the weak region
-    and — in weak mode with more than one rank — the c4 (512 samples, strong) region."""
+    and — with --full, in weak mode with more than one rank — the c4 (512 samples, strong) region."""
     import torch
     import torch.distributed as dist
 
@@ -638,7 +660,7 @@ def selftest_worker(args, world, rank):
     lo, hi = shard_range(total, rank, world) if args.total else (rank * args.batch, (rank + 1) * args.batch)
     ok, _ = region(total, lo, hi)
     c4 = None
-    if world > 1 and not args.total:  # the second timed region of a weak-scaling run
+    if args.full and world > 1 and not args.total:  # the second timed region of a weak-scaling run
         l4, h4 = shard_range(512, rank, world)
         ok4, _ = region(512, l4, h4)
         c4 = {"total": 512, "local": h4 - l4, "gather_ok": ok4, "scaling": "strong"}
@@ -700,14 +722,18 @@ def worker(args) -> int:
 
     # ---- synthetic inputs: same X, y on every rank; rank r owns forests offset .. offset+B-1
     wl = Workload(N, d, m, B, seed_base=N, rank_offset=offset, chunk=args.chunk, noise_seed=rank)
-    elapsed, call_ms, all_mll = timed_region(wl, args.steps, args.warmup, world, coll, make_gather(total))
+    elapsed, call_ms, all_mll = timed_region(wl, args.steps, args.warmup, world, coll, make_gather(total),
+                                             power_sampling=args.full)
     power_c3 = getattr(timed_region, "power", None)
     mll_host = wl.check()
     assert all_mll.shape[0] == total and bool(torch.isfinite(all_mll).all())
+    if args.dump_outputs and rank == 0:  # the last timed step's result, before anything below reuses the buffers
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "mll.npy"), all_mll.detach().cpu().numpy().astype(np.float64))
 
     # ---- c4 split (BASELINE configs[3]: 512 samples over the GPUs) as a second timed region in weak mode, N > 1
     c4 = None
-    if world > 1 and not strong and N == 4096:
+    if args.full and world > 1 and not strong and N == 4096:
         lo, hi = shard_range(512, rank, world)
         wl4 = Workload(N, d, m, hi - lo, seed_base=N, rank_offset=lo, noise_seed=rank)
         e4, call4, out4 = timed_region(wl4, args.steps, args.warmup, world, coll, make_gather(512))
@@ -726,22 +752,7 @@ def worker(args) -> int:
     value = total * steps / elapsed
     chol_flops = B * N**3 / 3.0  # algorithmic flops of one launch sequence (SURVEY §8d flops_chol x B)
     chol_tflops = chol_flops / (call_ms * 1e-3) / 1e12
-    traffic = hbm_traffic_from_profile(N, B, m)
     lib = wl.lib
-
-    # ---- one instrumented step (outside the timed region): per-kernel HIP-event spans inside the library
-    timing = _lib.MllTiming()
-    wl.run(timing)
-    breakdown = {k: round(float(getattr(timing, k)), 3) for k in ("total_ms", "gram_ms", "chol_ms", "diag_ms", "panel_ms", "solve_ms")}
-    kern = {}
-    for name, ms_key, n_key, fl_key in (("row_kernel", "panel_ms", "n_panel_launches", "panel_flops"),
-                                        ("solve_kernel", "solve_ms", "n_solve_launches", "solve_flops"),
-                                        ("diag_kernel", "diag_ms", "n_diag_launches", None)):
-        nl = int(getattr(timing, n_key))
-        ms = float(getattr(timing, ms_key))
-        kern[name] = {"launches_per_step": nl, "avg_ms": ms / max(nl, 1)}
-        if fl_key:
-            kern[name]["executed_tflops"] = float(getattr(timing, fl_key)) / (max(ms, 1e-9) * 1e-3) / 1e12
 
     result = {
         "metric": METRIC,
@@ -776,21 +787,40 @@ def worker(args) -> int:
             "peak": F64_MFMA_PEAK_TFLOPS,
             "unit": "TFLOP/s",
             "frac": chol_tflops / F64_MFMA_PEAK_TFLOPS,
-            "traffic": traffic["bytes_per_step"] if traffic else None,
-            "traffic_unit": "bytes of HBM traffic per step (one Cholesky launch sequence)",
-            "traffic_source": traffic if traffic else "no committed PMC profile matches this build (csrc digest %s) "
-                                                      "and workload" % csrc_digest(),
-            "power": power_c3,
             "algorithmic_flops_per_step": chol_flops,
             "call_ms": call_ms,
-            "instrumented_step_ms": breakdown,
-            "kernels": kern,
         },
     }
     if c4:
         result["c4_strong"] = c4
 
-    if world == 1:
+    if args.full:
+        # ---- one instrumented step (outside the timed region): per-kernel HIP-event spans inside the library
+        timing = _lib.MllTiming()
+        wl.run(timing)
+        breakdown = {k: round(float(getattr(timing, k)), 3)
+                     for k in ("total_ms", "gram_ms", "chol_ms", "diag_ms", "panel_ms", "solve_ms")}
+        kern = {}
+        for name, ms_key, n_key, fl_key in (("row_kernel", "panel_ms", "n_panel_launches", "panel_flops"),
+                                            ("solve_kernel", "solve_ms", "n_solve_launches", "solve_flops"),
+                                            ("diag_kernel", "diag_ms", "n_diag_launches", None)):
+            nl = int(getattr(timing, n_key))
+            ms = float(getattr(timing, ms_key))
+            kern[name] = {"launches_per_step": nl, "avg_ms": ms / max(nl, 1)}
+            if fl_key:
+                kern[name]["executed_tflops"] = float(getattr(timing, fl_key)) / (max(ms, 1e-9) * 1e-3) / 1e12
+        traffic = hbm_traffic_from_profile(N, B, m)
+        result["roofline"].update({
+            "traffic": traffic["bytes_per_step"] if traffic else None,
+            "traffic_unit": "bytes of HBM traffic per step (one Cholesky launch sequence)",
+            "traffic_source": traffic if traffic else "no committed PMC profile matches this build (csrc digest %s) "
+                                                      "and workload" % csrc_digest(),
+            "power": power_c3,
+            "instrumented_step_ms": breakdown,
+            "kernels": kern,
+        })
+
+    if args.full and world == 1:
         extras(args, wl, result, mll_host)
     out_file = os.environ.get("BARK_BENCH_LINE_FILE")
     if out_file:  # the launcher adds the live HBM counters and prints the line (live_traffic)

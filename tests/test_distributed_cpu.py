@@ -108,7 +108,7 @@ def _run_bench(argv, env_extra=None, timeout=180):
 def test_bench_launches_its_own_workers_from_a_plain_shell(gpus):
     """`python bench.py --gpus N` with no launcher around it: the parent (no torch, no GPU) starts N fresh workers,
     they rendezvous on 127.0.0.1, gather the per-rank MLL blocks and MAX-reduce the clock; rank 0 prints the line."""
-    r = _run_bench(["bench.py", "--gpus", str(gpus), "--selftest-launcher"])
+    r = _run_bench(["bench.py", "--gpus", str(gpus), "--selftest-launcher", "--full"])
     assert r["ranks_reached"] == gpus and r["gather_ok"] and r["launched_by"] == "bench.py"
     assert r["scaling"] == "weak" and r["total"] == 256 * gpus and r["local"] == 256
     if gpus > 1:  # the second timed region of a weak run: BASELINE configs[3], 512 samples sharded over the ranks
@@ -127,11 +127,11 @@ def test_bench_rccl_failure_is_fatal_unless_the_fallback_is_asked_for():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["BARK_BENCH_BACKEND"] = "nccl"
-    out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--selftest-launcher"], cwd=root, env=env,
+    out = subprocess.run([sys.executable, "bench.py", "--gpus", "2", "--selftest-launcher", "--full"], cwd=root, env=env,
                          capture_output=True, text=True, timeout=180)
     assert out.returncode != 0 and "--require-rccl is in force" in out.stderr
     assert not [l for l in out.stdout.splitlines() if l.startswith("{")]
-    r = _run_bench(["bench.py", "--gpus", "2", "--selftest-launcher", "--no-require-rccl"], {"BARK_BENCH_BACKEND": "nccl"})
+    r = _run_bench(["bench.py", "--gpus", "2", "--selftest-launcher", "--no-require-rccl", "--full"], {"BARK_BENCH_BACKEND": "nccl"})
     assert r["collective_backend_requested"] == "nccl" and r["collective_backend"] == "gloo" and r["rccl_ranks_seen"] is None
     assert r["gather_ok"] and r["c4_strong"]["gather_ok"]
 
@@ -147,6 +147,19 @@ def test_bench_runs_as_a_worker_under_torch_distributed_run():
     r = _run_bench(["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
                     "--master-port", str(_free_port()), "bench.py", "--gpus", "2", "--selftest-launcher"])
     assert r["ranks_reached"] == 2 and r["gather_ok"] and r["launched_by"] == "external"
+
+
+def test_plain_bench_run_leaves_the_secondary_regions_to_full():
+    """Without --full a run times only the headline region: no c4 region after a weak multi-rank run.  --steps below 1
+    (no timed step to divide by) is refused before any worker starts."""
+    import subprocess
+    import sys
+
+    r = _run_bench(["bench.py", "--gpus", "2", "--selftest-launcher"])
+    assert r["ranks_reached"] == 2 and r["gather_ok"] and r["c4_strong"] is None
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, "bench.py", "--steps", "0"], cwd=root, capture_output=True, text=True, timeout=60)
+    assert out.returncode == 2 and "--steps must be >= 1" in out.stderr
 
 
 def test_bench_parent_never_imports_torch():

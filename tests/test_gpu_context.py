@@ -915,3 +915,37 @@ def test_host_pointer_entry_points_refuse_what_they_cannot_do(env):
     assert rc == L.BARK_ERR_ARG and b"64" in lib.bark_last_error()
     assert lib.bark_tree_swap_eval_host_pair(ctx, L.ptr(K), N, None, pair.shape[1], ft.ctypes.data, d, L.ptr(Xd), 0.1, L.ptr(yd),
                                              scal.ctypes.data, r_out.ctypes.data, L.ptr(ws), ws.numel(), L.stream_ptr()) == L.BARK_ERR_ARG
+
+
+def test_bench_dumps_the_last_timed_steps_mll(env, tmp_path):
+    """`bench.py --dump-outputs DIR`: a plain run writes the (B,) MLL vector of its last timed step as DIR/mll.npy (float64).
+    Its inputs depend only on the arguments, so the file holds the bits this process computes for the same workload.  The
+    line carries the headline fields and none of what --full adds."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import bench
+
+    torch = env.torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    child_env = {k: v for k, v in os.environ.items()
+                 if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", "--n", "1024", "--batch", "8",
+                        "--dump-outputs", str(tmp_path)], cwd=root, env=child_env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    res = json.loads(lines[0])
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["ms_per_step"] > 0
+    assert res["unit"] == "evals/s" and res["higher_is_better"] is True and res["dtype"] == "f64" and res["metric"] == bench.METRIC
+    assert abs(res["value"] - 8 / (res["ms_per_step"] * 1e-3)) < 1e-6 * res["value"]
+    assert not set(res) & {"configs", "cpu_baseline", "leafspace_probe", "sampler_step", "c4_strong"}
+    assert not set(res["roofline"]) & {"kernels", "instrumented_step_ms", "power", "traffic", "gram_kernel"}
+    got = np.load(tmp_path / "mll.npy")
+    assert got.dtype == np.float64 and got.shape == (8,)
+    wl = bench.Workload(1024, 8, 50, 8, seed_base=1024, rank_offset=0, noise_seed=0)
+    wl.run()
+    torch.cuda.synchronize()
+    assert int(wl.info_d.abs().max().item()) == 0 and np.array_equal(got, wl.mll_d.cpu().numpy())

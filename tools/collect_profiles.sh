@@ -4,7 +4,7 @@ ROOT=$(pwd)
 OUT=$ROOT/gpurun_out/prof_${1:-r05}
 mkdir -p $OUT
 export PYTHONPATH=$ROOT
-python3 bench.py > $OUT/bench_c3_final.json 2> $OUT/bench.err || { echo bench failed; tail -5 $OUT/bench.err; exit 1; }
+python3 bench.py --full > $OUT/bench_c3_final.json 2> $OUT/bench.err || { echo bench failed; tail -5 $OUT/bench.err; exit 1; }
 for spec in "c3 4096 256 2" "b64 4096 64 3" "b16 4096 16 3" "b8 4096 8 3" "b1 4096 1 5" "c2 1024 1 10" "c5 16384 1 2" "c5_posterior 16384 1 1 10000" "n64 64 256 10" "n128 128 256 10" "n256 256 256 10" "n512 512 256 10" "n768 768 256 10"; do
   set -- $spec; label=$1; shift
   tools/kernel_trace.sh $label product "$@" > /dev/null || exit 1
@@ -21,7 +21,7 @@ rm -rf /tmp/ks
 # child would be spawned from a process whose preloaded profiler library may already have initialised the GPU.  With
 # the rank variables set, the program after `--` is the worker itself (bench.py main(): worker path, no new process).
 export RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29511
-timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -o t -- python3 $ROOT/bench.py --steps 3 --warmup 1 --cpu-sample 0 --no-configs > $OUT/bench_under_rocprof.json 2>/dev/null || { echo stats run failed; exit 1; }
+timeout -k 10 500 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks -o t -- python3 $ROOT/bench.py --full --steps 3 --warmup 1 --cpu-sample 0 --no-configs > $OUT/bench_under_rocprof.json 2>/dev/null || { echo stats run failed; exit 1; }
 f=$(find /tmp/ks -name "*kernel_stats.csv" | head -1)
 [ -n "$f" ] && cp $f $OUT/bench_c3_kernel_stats_final.csv
 unset RANK LOCAL_RANK WORLD_SIZE MASTER_ADDR MASTER_PORT
