@@ -71,6 +71,12 @@ int leafspace_inverse(const uint32_t *codes, int W, int npad, int N, const doubl
                       double *kinv_y, hipStream_t s);
 int leafspace_finish(const double *accum, const double *yy, const double *noise, const double *scale, int m, int bc, int N,
                      int include_2pi, double *mll, hipStream_t s);
+int64_t sample_spad(int64_t S);
+int64_t sample_partials(int64_t C, int64_t S);
+int sample_weights(const double *V, long ldv, long vstride, const double *w, const double *eps, int R, int Rpad, int S,
+                   int Spad, const double *noise, const double *scale, int m, int bc, double *Wt, hipStream_t s);
+int sample_gather(const uint32_t *ccodes, int W, int cpad, int C, const double *Wt, int Rpad, int Spad, int S, int m, int bc,
+                  int reduce, double *f, double *red, int64_t *ridx, double *part, int64_t *part_i, hipStream_t s);
 
 int launch_gram(const uint32_t *leaf1, int npad1, const uint32_t *leaf2, int npad2, int64_t B, int64_t m, int N, int M,
                 int Nout, int Mout, const double *shift, const double *scale, const double *noise, double *out, int64_t ld,
@@ -1357,15 +1363,17 @@ int bark_mll_batched_hip(bark_ctx *ctx, const void *packed, const bark_pack_info
 // ---------------------------------------------------------------------------------------------
 struct LeafLayout {
     Layout L;         // the R x R sweep workspace (N := R; candidates := R identity columns for the posterior)
-    int64_t R, Rpad, W, npad, Q, cpad;
-    size_t off_codes, off_planes, off_yy, off_ccodes, off_minv, off_w, off_wm, total;
+    int64_t R, Rpad, W, npad, Q, cpad, Spad;
+    size_t off_codes, off_planes, off_yy, off_ccodes, off_minv, off_w, off_wm, off_wt, off_part, off_part_i, total;
 };
 
 // C > 0: posterior at C candidates; want_inverse: explicit K_s^-1.  Either needs M^-1 (identity columns in the sweep).
+// S > 0 (with C > 0): S joint draws at the candidates instead, which need V = U^-T and w but not M^-1 itself.
 static LeafLayout make_leaf_layout(int64_t N, int64_t max_bits, int64_t m, int64_t Bc, int64_t C = 0,
-                                   bool want_inverse = false) {
+                                   bool want_inverse = false, int64_t S = 0) {
     LeafLayout g;
     const bool want_minv = C > 0 || want_inverse;
+    const bool sampling = S > 0;
     g.R = max_bits;
     g.Rpad = round_up(max_bits, NB);
     g.W = (max_bits + 31) / 32;
@@ -1383,11 +1391,18 @@ static LeafLayout make_leaf_layout(int64_t N, int64_t max_bits, int64_t m, int64
     g.off_ccodes = o;
     o = align256(o + (size_t)Bc * g.W * g.cpad * sizeof(uint32_t));
     g.off_minv = o;
-    if (want_minv) o = align256(o + (size_t)Bc * max_bits * max_bits * sizeof(double));
+    if (want_minv && !sampling) o = align256(o + (size_t)Bc * max_bits * max_bits * sizeof(double));
     g.off_w = o;
     if (want_minv) o = align256(o + (size_t)Bc * max_bits * sizeof(double));
     g.off_wm = o;
     if (want_inverse) o = align256(o + (size_t)Bc * N * max_bits * sizeof(double));
+    g.Spad = sampling ? sample_spad(S) : 0;
+    g.off_wt = o;
+    if (sampling) o = align256(o + (size_t)Bc * g.Rpad * g.Spad * sizeof(double));
+    g.off_part = o;
+    if (sampling) o = align256(o + (size_t)Bc * sample_partials(C, S) * sizeof(double));
+    g.off_part_i = o;
+    if (sampling) o = align256(o + (size_t)Bc * sample_partials(C, S) * sizeof(int64_t));
     g.total = o;
     return g;
 }
@@ -1402,24 +1417,41 @@ size_t bark_mll_leafspace_workspace_bytes(int64_t N, int64_t max_bits, int64_t m
     return make_leaf_layout(N, max_bits, m, Bc, C).total;
 }
 
+size_t bark_posterior_samples_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t Bc, int64_t C, int64_t S) {
+    if (N < 1 || max_bits < 1 || m < 1 || Bc < 1 || C < 1 || S < 1) return 0;
+    return make_leaf_layout(N, max_bits, m, Bc, C, false, S).total;
+}
+
 }  // extern "C"
 
-// shared driver of the leaf-space entry points: MLL always; posterior when C > 0; explicit inverse when kinv_out
+// Joint draws at the candidates (bark_posterior_samples_hip): S > 0, eps (B, S, R), and f_out (B, S, C) for
+// BARK_SAMPLE_FULL or red_out / idx_out (B, S) for BARK_SAMPLE_MAX / MIN.
+struct LeafDraws {
+    const double *eps = nullptr;
+    int64_t S = 0;
+    int reduce = BARK_SAMPLE_FULL;
+    double *f_out = nullptr, *red_out = nullptr;
+    int64_t *idx_out = nullptr;
+};
+
+// shared driver of the leaf-space entry points: MLL (unless mll_out is null and draws are asked for); posterior when C > 0;
+// explicit inverse when kinv_out; joint draws at the candidates when draws.S > 0
 static int leafspace_run(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d,
                          const double *y, const double *noise, const double *scale, int flags, const double *cand,
                          int64_t C, double *mll_out, double *mu_out, double *var_out, double *kinv_out,
                          double *kinv_y_out, int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc,
-                         void *stream_) {
+                         void *stream_, const LeafDraws &draws = LeafDraws()) {
     error_buffer()[0] = 0;
     int rc = check_ctx(ctx);
     if (rc) return rc;
-    if (!packed || !info || !X || !y || !noise || !mll_out || !info_out || !workspace)
+    const bool sampling = draws.S > 0;
+    if (!packed || !info || !X || !y || !noise || (!mll_out && !sampling) || !info_out || !workspace)
         return fail(BARK_ERR_ARG, "leaf-space entry: null argument");
     const int64_t B = info->B, m = info->m;
     if (N < 1 || d < 1 || B < 1 || Bc < 1 || C < 0 || N > (1 << 24) || C > (1 << 24))
         return fail(BARK_ERR_ARG, "bark_mll_leafspace_hip: bad shape N=%lld d=%lld B=%lld Bc=%lld C=%lld", (long long)N,
                     (long long)d, (long long)B, (long long)Bc, (long long)C);
-    if (C > 0 && (!cand || !mu_out || !var_out || !scale || !(flags & BARK_MLL_INCLUDE_SCALE)))
+    if (C > 0 && (!cand || (!sampling && (!mu_out || !var_out)) || !scale || !(flags & BARK_MLL_INCLUDE_SCALE)))
         return fail(BARK_ERR_ARG, "leaf-space posterior needs cand, mu_out, var_out, scale and BARK_MLL_INCLUDE_SCALE");
     if ((flags & BARK_MLL_INCLUDE_SCALE) && !scale) return fail(BARK_ERR_ARG, "BARK_MLL_INCLUDE_SCALE without scale");
     if (flags & BARK_MLL_RHS_IDENTITY) return fail(BARK_ERR_ARG, "leaf-space path computes the MLL only");
@@ -1428,7 +1460,7 @@ static int leafspace_run(bark_ctx *ctx, const void *packed, const bark_pack_info
     if (Bc > 65535) Bc = 65535;
     const bool want_minv = C > 0 || kinv_out != nullptr;
     if (kinv_out && info->max_bits > 65535) return fail(BARK_ERR_ARG, "leaf-space inverse: too many leaves");
-    const LeafLayout g = make_leaf_layout(N, info->max_bits, m, Bc, C, kinv_out != nullptr);
+    const LeafLayout g = make_leaf_layout(N, info->max_bits, m, Bc, C, kinv_out != nullptr, draws.S);
     if (workspace_bytes < g.total) return fail(BARK_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, g.total);
     if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(BARK_ERR_ARG, "workspace must be 256-byte aligned");
     if ((rc = set_lds_limits())) return rc;
@@ -1495,10 +1527,29 @@ static int leafspace_run(bark_ctx *ctx, const void *packed, const bark_pack_info
         }
         for (int j = 0; j < nrb; ++j)
             if ((rc = sw.step(j))) return rc;
-        rc = leafspace_finish(p.accum, yy, noise + c0, use_scale ? scale + c0 : nullptr, (int)m, (int)bc, (int)N,
-                              (flags & BARK_MLL_INCLUDE_2PI) ? 1 : 0, mll_out + c0, caller);
-        if (rc) return rc;
-        if (want_minv) {
+        if (mll_out) {
+            rc = leafspace_finish(p.accum, yy, noise + c0, use_scale ? scale + c0 : nullptr, (int)m, (int)bc, (int)N,
+                                  (flags & BARK_MLL_INCLUDE_2PI) ? 1 : 0, mll_out + c0, caller);
+            if (rc) return rc;
+        }
+        if (want_minv && sampling) {
+            // w = M^-1 v = V'z; then Wt = c w 1' + sqrt(scale/m) V' E' and the gather over the candidates' leaves (sample.hip)
+            const int R = (int)g.R, S = (int)draws.S;
+            if ((rc = launch_predict_reduce(p, R, R, (int)bc, nullptr, wvec, nullptr, g.L.splitk ? sw.slabs : nullptr, caller)))
+                return rc;
+            if ((rc = walk_one_hot(packed_c, &sub, cand, C, d, (int)g.W, ccodes, ctx->fault, caller))) return rc;
+            double *Wt = reinterpret_cast<double *>(ws + g.off_wt);
+            rc = sample_weights(p.A + (size_t)nrb * NB, p.ld, p.bstride, wvec, draws.eps + (size_t)c0 * S * R, R, (int)g.Rpad, S,
+                                (int)g.Spad, noise + c0, scale + c0, (int)m, (int)bc, Wt, caller);
+            if (rc) return rc;
+            const bool full = draws.reduce == BARK_SAMPLE_FULL;
+            rc = sample_gather(ccodes, (int)g.W, (int)g.cpad, (int)C, Wt, (int)g.Rpad, (int)g.Spad, S, (int)m, (int)bc,
+                               draws.reduce, full ? draws.f_out + (size_t)c0 * S * C : nullptr,
+                               full ? nullptr : draws.red_out + (size_t)c0 * S, full ? nullptr : draws.idx_out + (size_t)c0 * S,
+                               reinterpret_cast<double *>(ws + g.off_part), reinterpret_cast<int64_t *>(ws + g.off_part_i),
+                               caller);
+            if (rc) return rc;
+        } else if (want_minv) {
             // w = M^-1 v = V'z and M^-1 = V'V (the same kernels the dense posterior / inverse export use)
             const int R = (int)g.R;
             if ((rc = launch_predict_reduce(p, R, R, (int)bc, nullptr, wvec, nullptr, g.L.splitk ? sw.slabs : nullptr, caller)))
@@ -1552,6 +1603,30 @@ int bark_kernel_inverse_leafspace_hip(bark_ctx *ctx, const void *packed, const b
     }
     return leafspace_run(ctx, packed, info, X, N, d, y, noise, scale, flags, nullptr, 0, mll_out, nullptr, nullptr, kinv_out,
                          kinv_y_out, info_out, workspace, workspace_bytes, Bc, stream_);
+}
+
+int bark_posterior_samples_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N,
+                               int64_t d, const double *y, const double *noise, const double *scale, const double *cand,
+                               int64_t C, const double *eps, int64_t S, int reduce, double *f_out, double *red_out,
+                               int64_t *idx_out, int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc,
+                               void *stream_) {
+    error_buffer()[0] = 0;
+    if (reduce != BARK_SAMPLE_FULL && reduce != BARK_SAMPLE_MAX && reduce != BARK_SAMPLE_MIN)
+        return fail(BARK_ERR_ARG, "bark_posterior_samples_hip: unknown reduce %d", reduce);
+    if (!info || !cand || !eps || !scale || (reduce == BARK_SAMPLE_FULL ? !f_out : (!red_out || !idx_out)))
+        return fail(BARK_ERR_ARG, "bark_posterior_samples_hip: null argument");
+    if (C < 1 || S < 1 || S > (1 << 20))
+        return fail(BARK_ERR_ARG, "bark_posterior_samples_hip: bad shape C=%lld S=%lld", (long long)C, (long long)S);
+    if (info->m > 64) return fail(BARK_ERR_ARG, "leaf-space posterior samples support at most 64 trees (got %lld)", (long long)info->m);
+    LeafDraws draws;
+    draws.eps = eps;
+    draws.S = S;
+    draws.reduce = reduce;
+    draws.f_out = f_out;
+    draws.red_out = red_out;
+    draws.idx_out = idx_out;
+    return leafspace_run(ctx, packed, info, X, N, d, y, noise, scale, BARK_MLL_INCLUDE_SCALE, cand, C, nullptr, nullptr, nullptr,
+                         nullptr, nullptr, info_out, workspace, workspace_bytes, Bc, stream_, draws);
 }
 
 // out[b] = alpha * sum_i A[b][i] * y[i] + beta * c[b]  (one wave per row; fixed order; c may be null)

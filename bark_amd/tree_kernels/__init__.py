@@ -1,1 +1,7 @@
-from .tree_gps import BARKModel, forest_predict, mixture_of_gaussians_as_normal  # noqa: F401
+from .tree_gps import (  # noqa: F401
+    BARKModel,
+    forest_predict,
+    mixture_of_gaussians_as_normal,
+    posterior_sample_dim,
+    posterior_samples,
+)

@@ -6,17 +6,24 @@ blocked Cholesky with the candidate block appended as extra columns (V = U^-T K_
 mu = V'z and var = scale - colsumsq(V).  The reference's `diag=False` full (B, C, C) covariance is
 formed only on request (scale - V'V, one more MFMA product), from the same V.  The gpytorch `LeafGP`/`LeafMOGP` classes of
 the reference are out of scope.
+
+`posterior_samples` draws joint samples of the latent function at candidates from the leaf-space posterior of the
+leaf weights (bark_posterior_samples_hip), with the true covariance scale K_CC - K_CX K_s^-1 K_XC.  The reference's
+samplers (`bark.optimizer.thompson_sampling`, `nystrom`, `information_based_fidelity`) sit on a gpytorch model that
+no longer exists; `bark_amd.optimizer.thompson_sampling` builds on this one.
 """
 
 from __future__ import annotations
 
+import ctypes
+import os
 from typing import NamedTuple
 
 import numpy as np
 
 from .. import _lib
-from ..fitting.mll import _feat_types_of, _run, _run_leafspace
-from ..forest import _is_torch
+from ..fitting.mll import _feat_types_of, _fit_chunk, _raise_on_info, _run, _run_leafspace
+from ..forest import _as_nodes, _feat_types, _is_torch, _points, packed_forest
 
 
 class BARKModel(NamedTuple):
@@ -75,3 +82,124 @@ def mixture_of_gaussians_as_normal(mu, var):
     mu_y = np.mean(mu, axis=0)
     var_y = np.mean(var + mu**2, axis=0) - mu_y**2
     return mu_y, var_y
+
+
+_REDUCE = {None: _lib.SAMPLE_FULL, "max": _lib.SAMPLE_MAX, "min": _lib.SAMPLE_MIN}
+MAX_SAMPLE_TREES, MAX_SAMPLE_LEAVES = 64, 8192  # limits of the leaf-space posterior (include/bark_hip.h)
+
+
+def _forest3(forest):
+    nodes = _as_nodes(forest, 2)
+    return nodes.reshape(-1, *nodes.shape[-2:])
+
+
+def posterior_sample_dim(forest, domain) -> int:
+    """R, the width of the draws' `eps` (B, S, R): max_bits of the packed forest samples (the one-hot leaf-code width).
+    Host-side packer query; no GPU needed."""
+    nodes3 = _forest3(forest)
+    ft = _feat_types(_feat_types_of(domain))
+    info = _lib.PackInfo()
+    B, m, L = nodes3.shape
+    _lib.check(_lib.lib().bark_forest_pack_info(_lib.ptr(nodes3), B, m, L, _lib.ptr(ft), ft.shape[0], ctypes.byref(info)))
+    return int(info.max_bits)
+
+
+def _check_output_budget(nbytes: int, what: str):
+    """Refuse outputs larger than the HBM budget `_fit_chunk` works with (70 % of the free device memory, or
+    $BARK_WORKSPACE_GB): unlike the workspace they cannot be chunked."""
+    import torch
+
+    env = os.environ.get("BARK_WORKSPACE_GB")
+    if not env and nbytes <= (256 << 20):
+        return
+    if env:
+        budget = int(float(env) * (1 << 30))
+    else:
+        free, _total = torch.cuda.mem_get_info()
+        budget = int(0.7 * (free + _lib.workspace_bytes()))
+    if nbytes > budget:
+        raise ValueError(f"{what} needs {nbytes / 2**30:.2f} GiB, more than the {budget / 2**30:.2f} GiB budget: "
+                         "use reduce='max' / reduce='min' or fewer draws")
+
+
+def posterior_samples(model, data, candidates, domain, num_samples, *, generator=None, eps=None, reduce=None, chunk=None):
+    """Joint draws of the latent function (no observation noise) at the candidates, per forest sample.
+
+    model: the (forest, noise, scale) triple with leading dims flattened, as in `forest_predict`; `domain` may be
+    feat_types.  In leaf space (<= 64 trees, R <= 8192 leaves) the leaf weights have the posterior
+    W ~ N(c w, (scale/m) M^-1), so draw s of forest b is  f = c Z_C w + sqrt(scale/m) Z_C U^-1 eps[b, s]  with
+    M = U'U (include/bark_hip.h).  Its covariance is scale K_CC - K_CX K_s^-1 K_XC; `forest_predict(diag=False)`
+    keeps the reference's formula (scale 11' - ...) for parity and is not this covariance.
+
+    eps: (B, num_samples, R) standard normals (R = `posterior_sample_dim`), or None to draw them with one
+    `torch.randn` call on the device from `generator` (a torch.Generator, an int seed, or None: torch's default).
+    Returns (B, S, C) float64; with reduce="max" | "min" the pair (values (B, S), indices (B, S) int64) over the
+    candidates (ties: the lowest index).  Torch candidates give device tensors, numpy candidates numpy arrays."""
+    import torch
+
+    if reduce not in _REDUCE:
+        raise ValueError(f"unknown reduce {reduce!r} (use None, 'max' or 'min')")
+    S = int(num_samples)
+    if S < 1:
+        raise ValueError(f"num_samples must be >= 1, got {num_samples}")
+    forest, noise, scale = model
+    train_x, train_y = data
+    nodes3 = _forest3(forest)
+    ft = _feat_types(_feat_types_of(domain))
+    B, m = int(nodes3.shape[0]), int(nodes3.shape[1])
+    if m > MAX_SAMPLE_TREES:
+        raise ValueError(f"leaf-space posterior samples support at most {MAX_SAMPLE_TREES} trees (got {m})")
+    noise = np.ascontiguousarray(np.asarray(noise, dtype=np.float64).reshape(-1))
+    scale = np.ascontiguousarray(np.asarray(scale, dtype=np.float64).reshape(-1))
+    if noise.shape[0] != B or scale.shape[0] != B:
+        raise ValueError(f"noise/scale must have one entry per forest ({B})")
+    R = posterior_sample_dim(nodes3, ft)
+    if R > MAX_SAMPLE_LEAVES:
+        raise ValueError(f"leaf-space posterior samples support at most {MAX_SAMPLE_LEAVES} leaves per forest (got {R})")
+    if eps is not None and tuple(eps.shape) != (B, S, R):
+        raise ValueError(f"eps must have shape (B, num_samples, R) = {(B, S, R)}, got {tuple(eps.shape)}")
+    lib = _lib.lib()
+    Xd, _ = _points(train_x, ft.shape[0])
+    N, d = Xd.shape
+    dev = Xd.device
+    yd = _lib.to_device(train_y.detach() if _is_torch(train_y) else np.asarray(train_y, dtype=np.float64))
+    yd = yd.to(torch.float64).reshape(-1).contiguous()
+    if yd.shape[0] != N:
+        raise ValueError(f"y has {yd.shape[0]} rows, X has {N}")
+    cand_d, _ = _points(candidates, ft.shape[0])
+    C = int(cand_d.shape[0])
+    code = _REDUCE[reduce]
+    out_bytes = 8 * B * S * C if code == _lib.SAMPLE_FULL else 16 * B * S
+    _check_output_budget(out_bytes + (8 * B * S * R if eps is None else 0),
+                         "the full (B, S, C) output" if code == _lib.SAMPLE_FULL else "eps (B, S, R)")
+    if eps is None:
+        gen = generator
+        if isinstance(generator, (int, np.integer)):
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(int(generator))
+        eps_d = torch.randn((B, S, R), dtype=torch.float64, device=dev, generator=gen)
+    else:
+        eps_d = _lib.to_device(eps.detach() if _is_torch(eps) else np.asarray(eps, dtype=np.float64)).to(torch.float64)
+        eps_d = eps_d.contiguous()
+    pf = packed_forest(nodes3, ft)
+    noise_d, scale_d = _lib.to_device(noise), _lib.to_device(scale)
+    if code == _lib.SAMPLE_FULL:
+        f = torch.empty((B, S, C), dtype=torch.float64, device=dev)
+        red = idx = None
+    else:
+        f = None
+        red = torch.empty((B, S), dtype=torch.float64, device=dev)
+        idx = torch.empty((B, S), dtype=torch.int64, device=dev)
+    info = torch.empty(B, dtype=torch.int32, device=dev)
+    need = lambda k: int(lib.bark_posterior_samples_workspace_bytes(N, R, pf.m, k, C, S))  # noqa: E731
+    Bc = int(chunk) if chunk else _fit_chunk(B, need)
+    ws = _lib.workspace(need(Bc))
+    _lib.check(lib.bark_posterior_samples_hip(_lib.ctx(), _lib.ptr(pf.packed), pf.info_ref, _lib.ptr(Xd), N, d, _lib.ptr(yd),
+                                              _lib.ptr(noise_d), _lib.ptr(scale_d), _lib.ptr(cand_d), C, _lib.ptr(eps_d), S,
+                                              code, _lib.ptr(f), _lib.ptr(red), _lib.ptr(idx), _lib.ptr(info), _lib.ptr(ws),
+                                              ws.numel(), Bc, _lib.stream_ptr()))
+    _raise_on_info(info, "leaf-space system")
+    on_device = _is_torch(candidates)
+    if code == _lib.SAMPLE_FULL:
+        return f if on_device else f.cpu().numpy()
+    return (red, idx) if on_device else (red.cpu().numpy(), idx.cpu().numpy())

@@ -308,6 +308,31 @@ int bark_kernel_inverse_leafspace_hip(bark_ctx *ctx, const void *packed, const b
                                       void *workspace, size_t workspace_bytes, int64_t Bc, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Joint posterior draws of the latent function at C candidates, in the same leaf space (no observation noise).
+ * With M = I_R + c Z'Z = U'U, w = M^-1 Z'y and c = scale / (m s2) as above, f(x) = sum_t W[leaf_t(x)] and the leaf
+ * weights have the posterior  W ~ N(c w, (scale/m) M^-1).  The sweep with an identity right-hand side leaves
+ * V = U^-T (U^-1 U^-T = M^-1), so for each forest b and draw s:
+ *   f[b,s,x] = c_b sum_t w_b[col_t(x)] + sqrt(scale_b/m) sum_t (V_b' eps[b,s])[col_t(x)]
+ * i.e. cov_s(f(x), f(x')) = scale K(x, x') - K(x, X) K_s^-1 K(X, x'), the true posterior covariance (rank <= R, no C x C
+ * matrix and no jitter).  eps: (B, S, R) device, R = info->max_bits; column a of forest b is bit a of that forest's
+ * one-hot leaf code (the packer's order); entries a >= R_b (the forest's own leaf count) have no effect.
+ * reduce = BARK_SAMPLE_FULL: f_out (B, S, C).  BARK_SAMPLE_MAX / MIN: red_out (B, S) = max / min over the candidates
+ * of the same values, bit for bit, idx_out (B, S) int64 = its candidate index (ties: the lowest); f_out unused.
+ * Trees are summed in the fixed order t = 0..m-1: the draws do not depend on the launch shape.  Limits: m <= 64 trees,
+ * R <= 8192 (else BARK_ERR_ARG).  A non-positive-definite M is reported through info_out (k > 0) and a bad categorical
+ * value as -1, as on the leaf-space MLL path.  workspace >= bark_posterior_samples_workspace_bytes(N, R, m, Bc, C, S).
+ * ------------------------------------------------------------------------------------- */
+#define BARK_SAMPLE_FULL 0 /* f_out (B, S, C) */
+#define BARK_SAMPLE_MAX 1  /* red_out (B, S) = max over candidates, idx_out (B, S) int64 = its index */
+#define BARK_SAMPLE_MIN 2  /* ... min */
+size_t bark_posterior_samples_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t Bc, int64_t C, int64_t S);
+int bark_posterior_samples_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N,
+                               int64_t d, const double *y, const double *noise, const double *scale, const double *cand,
+                               int64_t C, const double *eps, int64_t S, int reduce, double *f_out, double *red_out,
+                               int64_t *idx_out, int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc,
+                               void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Woodbury / determinant-lemma updates — quick_inverse.py:13-33 (the per-tree step of the sampler,
  * bark_sampler.py:233-257).  With mul = -1 if `subtract` else +1:
  *   K_out         = K_inv - K_inv U (mul I + U' K_inv U)^-1 U' K_inv          (low_rank_inv_update)
