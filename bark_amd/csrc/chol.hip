@@ -24,16 +24,19 @@
 // appended as extra block columns, so the same sweep yields V = U^-T K_Xx; then mu = V'z,
 // var = scale - colsumsq(V), and optionally the full covariance / K_s^-1 = V'V (vtv_kernel).
 //
-// Three schedules of those kernels (Sweep, below), chosen per chunk of resident matrices:
-//   plain       diag(j) || row(j), then solve(j).  Chunks whose size is a multiple of the 256 CUs (every round of row
-//               workgroups full) and matrices of fewer than 8 block rows.
+// plan_chunk (below) picks one of eight schedules (BARK_SCHED_* in bark_hip.h) per chunk of resident matrices, and Sweep runs it:
+//   one launch  N <= 768, MLL only: the whole evaluation of a chunk in ONE kernel after the leaf walk — diag_kernel<true>
+//               (one block row), two_block_kernel (two), multi_block_kernel (three to six).
+//   plain       diag(j) || row(j), then solve(j).  Matrices of fewer than 8 block rows.
+//   paired      plain with two block rows per row launch: chunks whose size is a multiple of the 256 CUs (every round of row
+//               workgroups full), from 16 block rows on.
 //   pipelined   row(j) covers k < j-1 only and is launched two steps ahead on the helper streams; the last block row is
 //               applied by its consumers: solve_kernel<1> (one K = 256 product with the stacked [-U[j-1,j] W_j ; W_j])
 //               and diag_kernel (two block rows, and the -U[j-1,j] W_j block in its epilogue).  Under-filled launches
 //               split K.  Everything else that is not bound by its critical path.
-//   look-ahead  split-K layout (A materialised, slab scratch): the bulk of step j+2's K range (split into slabs) is
-//               launched after solve(j); diag(j) || the last block row's slab, reduce, solve(j) remain on the critical
-//               path.  Few small matrices (one N = 4096 matrix: 2.5 ms).
+//   split-K     split-K layout (A materialised, slab scratch) for few small matrices; with look-ahead, the bulk of step
+//               j+2's K range (split into slabs) is launched after solve(j), and diag(j) || the last block row's slab,
+//               reduce, solve(j) remain on the critical path (one N = 4096 matrix: 2.5 ms).
 //
 // Why left-looking: every U tile is written once and each trailing tile is accumulated in
 // registers over the whole K range, instead of a read-modify-write of the trailing matrix per
@@ -122,7 +125,7 @@ constexpr long LA_BULK_WORK = BARK_LA_BULK_WORK;
 // slabs (128 x 128) of one set: a split step has fewer than SPLITK_SLOTS / 2 tiles x matrices, each with S slabs
 // (tiles x matrices x S <= the slots aimed at) plus one for the last block row
 constexpr size_t SLAB_SET_TILES = (LA_SLOTS > SPLITK_SLOTS ? LA_SLOTS : SPLITK_SLOTS) + SPLITK_SLOTS / 2;
-// look-ahead from this much bulk work on ((tiles x matrices) x block rows; see Sweep::lookahead).  Re-measured with this round's
+// look-ahead from this much bulk work on ((tiles x matrices) x block rows; see lookahead()).  Re-measured with this round's
 // shorter chain, same box, 450 | 600: N = 4096 x 2 2.28 | 2.45 ms, N = 6000 x 1 3.27 | 3.64, N = 5600 x 1 3.07 | 3.18, nothing
 // else moves; from 200 down the lone N = 4096 matrix and N = 2048 x 4 get look-ahead steps and lose 7-15 %
 #ifndef BARK_LA_MIN_WORK
@@ -171,26 +174,16 @@ constexpr long TAIL_MAX_WGS = BARK_TAIL_MAX_WGS;  // ragged_tail: largest last r
 // Below 8 block rows (no pipelining) the rule is the tile count alone.
 constexpr int SPLITK_LAYOUT_MAX_TILES = BARK_SPLITK_LAYOUT_MAX_TILES;
 constexpr int64_t SPLITK_LAYOUT_MAX_WORK = BARK_SPLITK_LAYOUT_MAX_WORK;
-// Build-time tuning constants of the pipelined schedule (numbers only: every on/off alternative that was measured and
-// lost is gone from the sources, with its figures left in the comment next to the code that won).
-#ifndef BARK_DIAG_WAVES8
-#define BARK_DIAG_WAVES8 1  // chain-bound diag launches (a CU per matrix) with eight waves: factor_tile8
-#endif
-constexpr int DIAG8_MAX_BC = 256;  // one-launch kernels (N <= 256): eight waves up to this many matrices per chunk
-#ifndef BARK_WALK_IN_KERNEL
-#define BARK_WALK_IN_KERNEL 1  // N <= 128 (eight-wave diag_kernel<true>): the leaf walk inside the kernel, no walk launch
-#endif
-#ifndef BARK_TWO_BLOCK
-#define BARK_TWO_BLOCK 1  // 128 < N <= 256, MLL only: the one-launch evaluation by two_block_kernel (0: the multi-launch sweep)
-#endif
-// ... for chunks of TWO_MIN_BC .. TWO_MAX_BC matrices, and larger chunks up to TWO_ANY_BC_MAX_N points (plan_chunk has the table)
+// Build-time tuning constants (numbers only: every on/off alternative that was measured and lost is gone from the sources,
+// with its figures left in the comment next to the code that won).
+constexpr int DIAG8_MAX_BC = 256;  // one-launch kernels (N <= 256): eight waves (factor_tile8) up to this many matrices per chunk
+// 128 < N <= 256, MLL only: the one-launch evaluation by two_block_kernel for chunks of TWO_MIN_BC .. TWO_MAX_BC matrices, and
+// larger chunks up to TWO_ANY_BC_MAX_N points (plan_chunk has the table)
 #ifndef BARK_TWO_MIN_BC
 #define BARK_TWO_MIN_BC 1
 #endif
 constexpr int TWO_MIN_BC = BARK_TWO_MIN_BC, TWO_MAX_BC = 384, TWO_ANY_BC_MAX_N = 224;
-#ifndef BARK_MULTI_BLOCK
-#define BARK_MULTI_BLOCK 1  // 256 < N <= 768, MLL only: the one-launch evaluation by multi_block_kernel
-#endif
+// 256 < N <= 768, MLL only: the one-launch evaluation by multi_block_kernel.
 // Chunks of at least MB_MIN_BC4 (four block rows) / MB_MIN_BC3 (three) matrices: the kernel runs a matrix's block steps one after the
 // other on ONE CU (~0.35 ms at N = 512 whatever the batch), the sweep spreads a matrix over the chip.  Round 5, same box, one process per
 // variant, sweep | multi_block_kernel, ms (with the kernel's three-stage ring really in flight; before that the window was 160 .. 320):
@@ -246,15 +239,6 @@ constexpr int PLAIN_CHUNK_MULTIPLE = BARK_PLAIN_CHUNK_MULTIPLE;  // chunks of a 
 // test_sixteen_block_rows_b256_is_the_boundary_of_the_paired_schedule
 #ifndef BARK_PLAIN_MIN_NRB
 #define BARK_PLAIN_MIN_NRB 16
-#endif
-#ifndef BARK_PIPE_SYRK_MODE
-#define BARK_PIPE_SYRK_MODE 2  // pipelined schedule's row launches: 1 = SYRK workgroup in its matrix's run of tiles, 2 = after all square tiles
-#endif
-#ifndef BARK_PLAIN_PAIRS
-#define BARK_PLAIN_PAIRS 1  // lock-step chunks of the plain schedule: two block rows per row launch (Sweep::step_paired)
-#endif
-#ifndef BARK_PLAIN_SYRK_MODE
-#define BARK_PLAIN_SYRK_MODE 2  // 0: square diagonal tile; 2: SYRK workgroups after all square tiles (launch_rows)
 #endif
 constexpr int PLAIN_MIN_NRB = BARK_PLAIN_MIN_NRB;
 #ifndef BARK_SOLVE_NARROW_MAX_WGS
@@ -384,30 +368,215 @@ int set_lds_limits() {
 namespace {
 
 // ---------------------------------------------------------------------------------------------
-// Sweep: the factorisation of one chunk of resident matrices, shared by the dense MLL / posterior entry
-// point and the leaf-space entry point.  The caller fills the matrices (and right-hand sides), then calls
-// step(j) for every block column.
+// The shape of a sweep, and the rules that depend on nothing but the shape, the chunk size bc and the block step j: Sweep
+// launches what they say, and plan_chunk counts from the same functions what a chunk will run.
 // ---------------------------------------------------------------------------------------------
-struct Sweep {
-    Mats p;
-    hipStream_t main = nullptr, panel = nullptr;  // panel == main: no overlap
-    hipStream_t la_stream = nullptr;              // look-ahead launches of the split-K bulk (null: no look-ahead)
-    hipStream_t la_stream2 = nullptr;             // ... of the odd steps (consecutive bulks do not queue behind each other)
-    int nrb_steps = 0;                            // block columns that get a step() (== nrb)
-    bark_ctx *res = nullptr;
-    int nrb = 0, ncb = 0;
-    bool fused = false, splitk = false, pipelined = false;
-    bool paired = false;  // plain schedule with two block rows per row launch (step_paired)
+struct SweepShape {
+    int nrb = 0, ncb = 0;  // block rows; block columns incl. the candidate (or identity) blocks
+    int N = 0, nW = 0;     // real points; leaf-code words per point (0: no codes, the caller fills A)
+    bool splitk = false;   // split-K layout: slab scratch reserved, A materialised (the reduce kernel reads it)
+    bool fused = false;    // A generated inside the row kernels; only the tile (0, 0) is materialised (input of diag(0))
+};
+// MLL-only sweeps generate A inside the row kernels while a tile's two code strips fit the GEMM stage's LDS; with candidate
+// columns (or split-K) the whole matrix is filled up front
+SweepShape make_shape(const Layout &L, int64_t N, int leaf_words) {
+    SweepShape s;
+    s.nrb = (int)(L.npad / NB);
+    s.ncb = (int)(L.ncols / NB);
+    s.N = (int)N;
+    s.nW = leaf_words;
+    s.splitk = L.splitk;
+    s.fused = leaf_words > 0 && !L.splitk && L.cpad == 0 && (size_t)2 * leaf_words * NB * sizeof(uint32_t) <= GEMM_LDS;
+    return s;
+}
+// tiles of block row j: the ones right of the diagonal and the partial diagonal tile (none in the last block row)
+inline int tiles_of(const SweepShape &s, int j) { return (s.ncb - j - 1) + ((j + 1 < s.nrb) ? 1 : 0); }
+
+// split-K factor of step j over nkb block rows: fill ~SPLITK_SLOTS workgroup slots, >= 1 block row per slab
+int split_factor(const SweepShape &s, int bc, int j, int nkb, int slots = SPLITK_SLOTS) {
+    const int n_tiles = tiles_of(s, j);
+    if (!s.splitk || j < 1 || n_tiles <= 0 || n_tiles * bc >= SPLITK_SLOTS / 2 || nkb < 1) return 1;
+    int S = slots / (n_tiles * bc);
+    if (slots != SPLITK_SLOTS) {  // look-ahead bulk: aim at `slots` workgroups (nearest S), never more than SPLITK_SLOTS
+        S = (2 * slots + n_tiles * bc) / (2 * n_tiles * bc);
+        while (S > 1 && S * n_tiles * bc > SPLITK_SLOTS) --S;
+    }
+    if (S < 1) S = 1;
+    // a slab on the critical path (the plain split of an under-filled step) may be shorter than a block row: its workgroup is
+    // bound by the latency of its k-tiles' DMA stages (~2.7 us each on an idle chip, 8 per block row), not by their MFMAs
+    int cap = nkb;
+    if (slots == SPLITK_SLOTS && (long)n_tiles * bc * nkb * SPLIT_FINE <= SPLIT_FINE_MAX_WGS) cap = nkb * SPLIT_FINE;  // (see SPLIT_FINE)
+    if (S > cap) S = cap;
+    if (S > SPLITK_MAX) S = SPLITK_MAX;
+    return S;
+}
+// look-ahead step: split layout, under-filled, and at least one block row besides the last (j >= 2)
+// ... and a bulk worth a launch of its own: (tiles x matrices) x block rows >= LA_MIN_WORK, i.e. ~40 us of MFMA
+// work (4.2 MFLOP per tile and block row); below that the step is bound by diag_kernel and the extra launches and
+// events only cost (lone N = 4096: 2.88 ms without, 3.11 ms with look-ahead everywhere)
+bool lookahead(const SweepShape &s, int bc, int j) {
+    if (j < 2 || j >= s.nrb || split_factor(s, bc, j, j) <= 1) return false;
+    return (long)tiles_of(s, j) * bc * (long)(j - 1) >= LA_MIN_WORK;
+}
+int la_slots(const SweepShape &s, int bc, int j) {  // look-ahead step j: workgroups its bulk (block rows [0, j-1)) aims at
+    return (long)tiles_of(s, j) * bc * (long)(j - 1) >= LA_BULK_WORK ? LA_SLOTS : LA_SLOTS_CHAIN;
+}
+// Ragged last round (chunks that are NOT in the split-K layout): n_tiles x Bc workgroups rarely fill whole rounds
+// of the chip's SPLITK_SLOTS slots, and the stragglers of the last round run one per CU for a full tile time
+// (measured at B = 64: up to 35 % per step when one tile in nine is left over).  The tiles beyond the last full
+// round are split over K instead, so that they finish in a fraction of a round: -> first tile of the tail and its
+// split factor (tail == tiles_of(j): nothing to split).
+void ragged_tail(const SweepShape &sh, int bc_, int j, int &tail, int &S) {
+    const int n_tiles = tiles_of(sh, j);
+    tail = n_tiles;
+    S = 1;
+    if (sh.splitk || j < 2 || n_tiles <= 0) return;
+    const long bc = bc_, slots = SPLITK_SLOTS;
+    const long rounds = (n_tiles * bc) / slots;
+    const long n_plain = rounds * slots / bc;  // tiles that fill whole rounds
+    if (n_plain * bc != rounds * slots) return;  // rounds do not end on a tile boundary (Bc does not divide the slots)
+    const long m = n_tiles - n_plain;
+    // worth it for a sparse last round only (a slab round trip and two more launches): measured at N = 4096,
+    // B = 64 27.8 -> 27.0 ms, B = 48 22.8 -> 21.8 ms; a half-filled last round (B = 256, odd tile counts) gains nothing
+    if (m <= 0 || m * bc > TAIL_MAX_WGS) return;
+    long s = slots / (m * bc);
+    if (s > j) s = j;
+    if (s > SPLITK_MAX) s = SPLITK_MAX;
+    if (s < 3) return;  // a 2-way split of a third-filled round measured slower than leaving it (B = 64, j = 5, 13, 21)
+    tail = (int)n_plain;
+    S = (int)s;
+}
+// pipelined schedule: the row launch of block row j ("bulk") covers the block rows [0, kdone(j)) of its K range
+inline int kdone(int j) { return j > 0 ? j - 1 : 0; }
+// a K = 0 launch only generates A (fused sweeps); with a materialised A there is nothing to do
+inline bool has_bulk(const SweepShape &s, int j) { return j < s.nrb && tiles_of(s, j) > 0 && (kdone(j) > 0 || s.fused); }
+// the last block rows have few tiles and the longest K: below half a round of workgroups the bulk splits K into this many
+// slabs (S >= 2; slabs + generating reduce, both on the bulk stream, off the critical path; slab sets alternate with j like
+// the bulk streams).  N = 4096, B = 32: the last 8 steps took 3.5 of 13.9 ms.
+int pipe_split(const SweepShape &s, int bc, int j) {
+    const int k = kdone(j), nt = tiles_of(s, j);
+    int S = 1;
+    if (k >= 2 && nt * bc < SPLITK_SLOTS / 2) {
+        S = (2 * PIPE_BULK_SLOTS + nt * bc) / (2 * nt * bc);
+        if (S > k) S = k;
+        if (S > SPLITK_MAX) S = SPLITK_MAX;
+        while (S > 1 && S * nt * bc > SPLITK_SLOTS) --S;
+    }
+    return S;
+}
+
+// Which schedule a chunk of bc resident matrices takes — the ONE place that decides it: both entry points configure their
+// Sweep from it (Sweep::configure), and bark_mll_plan_query reports it (DESIGN.md section 4 has the table for the BASELINE
+// configs; a -m gpu test asserts it, so that a tuning constant cannot silently move the headline shape onto another schedule).
+struct ChunkPlan {
+    bool one_block;  // the whole evaluation of the chunk in one launch after the leaf walk (OneBlock)
+    bool pipelined;  // Sweep::step_pipelined
+    bool paired;     // plain schedule with two block rows per row launch (Sweep::step_paired)
+    bool lockstep;   // a multiple of PLAIN_CHUNK_MULTIPLE matrices: every round of row workgroups is full
     // chain-bound chunks (few matrices): diag_kernel(j) itself waits, at its end, for the row launch solve(j) depends on
     // (device-side progress counter) instead of an event wait on the caller's stream; see diag_kernel
-    bool dev_wait = false;
-    bool pre_update = false;  // ... and the rank-128 / 256 update of the diagonal tile runs as diag_pre_kernel
-    // MLL-only sweeps: the last diag_kernel launch of the chunk writes the MLL itself (fin_mll != nullptr); `finished` says it did
-    double *fin_mll = nullptr;
-    const int32_t *fin_fault = nullptr;
-    int fin_2pi = 0;
+    bool dev_wait;
+    bool dev_gate;    // ... and the helper streams are released by gate kernels instead of an event record
+    bool pre_update;  // chain-bound split-K chunks: the rank-128 update of the diagonal tile runs as diag_pre_kernel
+    int lookahead_steps, splitk_steps;  // block steps with a look-ahead bulk / with any split-K launch (reported only)
+};
+// Dense: the MLL / posterior / inverse sweep of bark_mll_batched_hip.  LeafSpace: the R x R systems of the leaf-space entry
+// points (a block row or two; the caller fills A and the right-hand sides): no one-launch kernels, no paired schedule, no
+// device-side hand-over — event joins are fine there.
+enum class SweepPath { Dense, LeafSpace };
+ChunkPlan plan_chunk(const SweepShape &s, int64_t bc, bool timing, bool dev_wait_ok, bool two_streams, SweepPath path) {
+    ChunkPlan c{};
+    const int nrb = s.nrb;
+    const bool dense = path == SweepPath::Dense, mll_only = s.ncb == s.nrb;
+    // Pipelined schedule: pays whenever the plain schedule leaves ragged rounds of workgroups (measured at N = 4096:
+    // B = 40 +15 %, 64 +7 %, 96 +9 %, 160 +5 %, 192 +4 %; N = 8192, B = 32 +7 %; N = 2048, B = 128..192 +5 %).  When Bc
+    // is a multiple of the 256 CUs every round of the plain schedule is full or exactly half full; the two then tie at
+    // N = 4096 (93.6 | 93.7 ms at B = 256), the plain one wins beyond (B = 512: 186.6 | 188.6; N = 8192, B = 256:
+    // 696 | 711) and the pipelined one up to 16 block rows (N = 2048: 14.1 | 13.8, N = 1024: 2.65 | 2.56).  Fewer than 8
+    // block rows: no difference measured (N = 512..896), plain.
+    const bool pipeline_ok = !s.splitk && nrb >= PIPE_MIN_NRB;
+    c.lockstep = bc % PLAIN_CHUNK_MULTIPLE == 0;
+    c.pipelined = pipeline_ok && (!c.lockstep || nrb < PLAIN_MIN_NRB);
+    // N <= 128: leaf walk + ONE launch per chunk (OneBlock); 128 < N <= 256: the same with the two-block kernel (two_block_kernel),
+    // while the codes of 256 points fit behind the factor image in LDS (up to 83 code words per point)
+    // ... and while it is the faster form (a workgroup runs its matrix's phases one after the other; the multi-launch sweep spreads a
+    // lone matrix over the chip and overlaps the phases of many): round 5, same box, sweep | two_block_kernel, ms —
+    //   N = 256:  x 1..8 0.103-0.105 | 0.107-0.109 (four waves; with eight waves and the tile generation over all of them 0.098 | 0.088: every
+    //             batch size from 1 on since),  x 256 0.158 | 0.133,  x 512 0.247 | 0.257,  x 1024 0.486 | 0.502,  x 2048 0.88 | 0.96
+    //   N = 200:  x 32 0.105 | 0.097,  x 256 0.156 | 0.118,  x 512 0.245 | 0.227,  x 1024 0.473 | 0.447      N = 144 x 1024  0.468 | 0.400
+    const bool two_ok = nrb == 2 && DIAG_LDS + (size_t)s.nW * 2 * NB * sizeof(uint32_t) + 2 * NB * sizeof(double) <= DIAG_LDS_EXCLUSIVE &&
+                        bc >= TWO_MIN_BC && (bc <= TWO_MAX_BC || s.N <= TWO_ANY_BC_MAX_N);
+    c.one_block = dense && (nrb == 1 || two_ok) && s.fused && mll_only && !timing;
+    // 256 < N <= 768: multi_block_kernel (three to six block rows in one launch, eight waves), whatever layout the sweep would
+    // take for the chunk, while the codes of the matrix's points fit beside the factor image and the GEMM stages in LDS
+    if (dense && nrb >= 3 && nrb <= MB_MAX_NRB && mll_only && !timing && mb_chunk_ok(nrb, bc) && mb_lds_bytes(s.nW, nrb) <= DIAG_LDS_EXCLUSIVE)
+        c.one_block = true;
+    if (c.one_block) {
+        c.pipelined = false;
+        return c;
+    }
+    c.paired = dense && !c.pipelined && !s.splitk && nrb >= PLAIN_MIN_NRB && c.lockstep && two_streams;
+    c.dev_wait = dense && dev_wait_ok && (s.splitk || c.pipelined) && bc <= DEVWAIT_MAX_BC;
+    // gate kernels in place of the event record that releases the row streams: measured (one process per variant,
+    // gates | end-of-diag wait only | events, ms): pipelined N = 4096 x 8 4.44 | 4.59 | 4.64, N = 8192 x 2 8.18 | 8.35 |
+    // 8.48; split-K layout N = 4096 x 1 2.19 | 2.14 | 2.22, N = 1024 x 1 0.575 | 0.520 | 0.534 — pipelined only
+    // ... split-K layout: only for sweeps with look-ahead steps (N = 6900 x 1 5.02 -> 4.59 with gates; without look-ahead
+    // they cost: N = 4096 x 1 2.04 -> 2.28, N = 2048 x 4 1.09 -> 1.21)
+    c.dev_gate = c.dev_wait && c.pipelined;
+    const int b = (int)bc;
+    if (!c.pipelined && !c.paired) {
+        for (int j = 1; j < nrb; ++j) {
+            const bool la = lookahead(s, b, j);
+            c.lookahead_steps += la ? 1 : 0;
+            c.splitk_steps += (la || split_factor(s, b, j, j) > 1) ? 1 : 0;
+        }
+        if (c.dev_wait && c.lookahead_steps > 0) c.dev_gate = true;
+    } else if (c.pipelined) {
+        for (int j = 0; j < nrb; ++j) c.splitk_steps += (has_bulk(s, j) && pipe_split(s, b, j) >= 2) ? 1 : 0;
+    }
+    // split-K layout only: same box, this | inside diag_kernel, ms — N = 4096 x 1 2.035 | 2.130, N = 1024 x 1 0.492 | 0.514,
+    // N = 2048 x 4 1.082 | 1.125; in the pipelined schedule the extra launch queues for slots behind the resident row
+    // workgroups like every kernel of the chain does (N = 4096 x 8 4.77 | 4.46, x 16 7.61 | 7.11, N = 16384 x 1 27.2 | 25.4)
+    c.pre_update = dense && s.splitk && bc <= DEVWAIT_MAX_BC;
+    return c;
+}
+int plan_code(const ChunkPlan &c, const SweepShape &s) {
+    if (c.one_block) return s.nrb >= 3 ? BARK_SCHED_MULTI_BLOCK : s.nrb == 2 ? BARK_SCHED_TWO_BLOCK : BARK_SCHED_ONE_BLOCK;
+    if (c.paired) return BARK_SCHED_PAIRED;
+    if (c.pipelined) return BARK_SCHED_PIPELINED;
+    if (s.splitk) return c.lookahead_steps > 0 ? BARK_SCHED_SPLITK_LOOKAHEAD : BARK_SCHED_SPLITK;
+    return BARK_SCHED_PLAIN;
+}
+
+// f(std::integral_constant<int, GEN>()) for the GEN instantiation of a kernel that may generate A (row_kernel,
+// panel_reduce_kernel): 0 reads the materialised A, 1 + rep generates it from leaf codes of representation rep (LeafRep)
+template <class F> void with_gen(bool fused, int rep, F &&f) {
+    if (!fused)
+        f(std::integral_constant<int, 0>());
+    else if (rep == REP_BITS)
+        f(std::integral_constant<int, 1 + REP_BITS>());
+    else if (rep == REP_BYTES7)
+        f(std::integral_constant<int, 1 + REP_BYTES7>());
+    else
+        f(std::integral_constant<int, 1 + REP_BYTES8>());
+}
+
+// ---------------------------------------------------------------------------------------------
+// Sweep: the factorisation of the chunks of resident matrices of one call, shared by the dense MLL / posterior entry
+// point and the leaf-space entry points.  Per chunk the caller configures it from the chunk's plan, fills the matrices
+// (and right-hand sides), then runs factor(); for_chunks walks the chunks.
+// ---------------------------------------------------------------------------------------------
+struct Sweep {
+    SweepShape sh;
+    ChunkPlan plan{};  // of the current chunk (configure)
+    Mats p{};
+    hipStream_t main = nullptr, panel = nullptr;  // panel == main: no overlap
+    hipStream_t la_stream = nullptr;              // look-ahead launches of the split-K bulk; the pipelined schedule's odd bulks
+    hipStream_t la_stream2 = nullptr;             // ... of the odd steps (consecutive bulks do not queue behind each other)
+    bark_ctx *res = nullptr;
+    // MLL-only sweeps: the last diag_kernel launch of the chunk writes the MLL itself (fin.mll != nullptr); `finished` says it did
+    OneBlock fin{};
     bool finished = false;
-    bool dev_gate = false;  // ... and the helper streams are released by gate kernels instead of an event record
     int rep = 0;
     double *slabs = nullptr;
     // timing mode only: one event pair per launch, recorded on the stream of the launch
@@ -415,6 +584,34 @@ struct Sweep {
     std::vector<hipEvent_t> ev;
     std::vector<size_t> gram_marks, diag_marks, panel_marks, solve_marks;
     double panel_flops = 0.0, solve_flops = 0.0;
+
+    // the sweep over the workspace laid out by L, on the caller's stream and the context's helper streams (ctx_events made them)
+    Sweep(bark_ctx *ctx, hipStream_t caller, const Layout &L, void *workspace, const SweepShape &shape, int m, int leaf_rep = 0,
+          bool timing = false)
+        : sh(shape), main(caller), panel(ctx->helper), la_stream(ctx->helper2), la_stream2(ctx->helper3), res(ctx), rep(leaf_rep),
+          timed(timing) {
+        char *ws = static_cast<char *>(workspace);
+        slabs = reinterpret_cast<double *>(ws + L.off_slab);
+        p.A = reinterpret_cast<double *>(ws + L.off_A);
+        p.ld = L.ld;
+        p.bstride = L.npad * L.ld;
+        p.W = reinterpret_cast<double *>(ws + L.off_W);
+        p.yz = reinterpret_cast<double *>(ws + L.off_yz);
+        p.accum = reinterpret_cast<double *>(ws + L.off_acc);
+        p.sync = reinterpret_cast<int32_t *>(ws + L.off_sync);
+        p.nrb = sh.nrb;
+        p.ncb = sh.ncb;
+        p.nW = sh.nW;
+        p.m = m;
+        p.N = sh.N;
+    }
+    // every per-chunk setting of the sweep, from the chunk's plan
+    void configure(const ChunkPlan &c, int64_t bc, const OneBlock &fin_mll = OneBlock{}) {
+        plan = c;
+        p.Bc = (int)bc;
+        fin = fin_mll;
+        finished = false;
+    }
 
     // Helper streams this call has put work on (bit i: res->helper / helper2 / helper3).  Whatever way the call ends, every
     // one of them is joined back into the caller's stream (rejoin_helpers): under stream capture a forked stream that is not
@@ -460,6 +657,33 @@ struct Sweep {
         for (hipEvent_t e : ev) (void)hipEventDestroy(e);  // timing events of a call that did not reach report()
     }
 
+    // chunk(c0, bc) for the chunks of (at most) Bc of the B matrices, one after the other.  However it ends, no helper stream
+    // is left forked from the caller's (under capture: unjoined)
+    template <class F> int for_chunks(int64_t B, int64_t Bc, F &&chunk) {
+        int rc = BARK_OK;
+        for (int64_t c0 = 0; c0 < B && rc == BARK_OK; c0 += Bc) rc = chunk(c0, (B - c0 < Bc) ? (B - c0) : Bc);
+        // an error return from the middle of a chunk: a gate kernel of a helper stream may be waiting for a diag_kernel that
+        // will now never be launched: raise the sticky time-out word first, so that it gives up at once instead of holding
+        // the rejoin for its 2 s bound (best effort)
+        if (rc && plan.dev_gate) {
+            hipLaunchKernelGGL(sync_publish_kernel, dim3(1), dim3(1), 0, main, p.sync, 2, 1);
+            (void)hipGetLastError();
+        }
+        rejoin_helpers();  // whatever is still marked touched (joined() clears a stream's mark when an event join covers it)
+        return rc;
+    }
+    // the block steps of the configured chunk
+    int factor() {
+        int r;
+        for (int j = 0; j < sh.nrb; ++j)
+            if ((r = step(j))) return r;
+        // device-side hand-over: nothing has joined the helper streams to the caller's yet (the last diag_kernel waited for
+        // their counters; after a time-out it did not).  One event join per touched stream and chunk, so that neither the next
+        // chunk's prologue nor the caller's next use of the workspace can overtake a row launch of this one.
+        if (plan.dev_wait) rejoin_helpers();
+        return BARK_OK;
+    }
+
     int mark_on(hipStream_t s) {
         if (!timed) return BARK_OK;
         hipEvent_t e;
@@ -478,22 +702,16 @@ struct Sweep {
     //      the launch: n_tiles == n_right + 1): the square tiles keep their lock step and the short workgroups fill — or are —
     //      the last round.  Plain, same box, square diagonal tile | this: N = 4096 x 256 95.3 | 92.4 ms, x 512 189.3 | 183.6,
     //      N = 4200 x 256 104.6 | 101.5, N = 8192 x 256 715 | 703; pipelined, mode 1 | 2: N = 4096 x 64 24.04 | 23.67, x 192
-    //      70.6 | 69.9, N = 2200 x 256 18.54 | 18.32.  Shipped in both schedules (BARK_PLAIN_SYRK_MODE, BARK_PIPE_SYRK_MODE).
+    //      70.6 | 69.9, N = 2200 x 256 18.54 | 18.32.  Shipped in both schedules.
     //   (a third form — the SYRK workgroups as a launch of their own on another stream, released with solve(j), which does not
     //   need them — measured slower: 92.7-96.0 against 91.4-92.5 ms; profiles/r04/headline_power_wall.txt item 6)
     int launch_rows(hipStream_t st, int j, int kdone, int n_right, int n_tiles, int syrk) {
         if (syrk == 2 && n_tiles != n_right + 1) syrk = 0;
         const unsigned diag_wgs = (unsigned)(NXCD * ((p.Bc + NXCD - 1) / NXCD));
         const unsigned grid = syrk == 2 ? xcd_grid(n_right, p.Bc) + diag_wgs : xcd_grid(n_tiles, p.Bc);
-        const dim3 g(grid), blk(THREADS);
-        if (!fused)
-            hipLaunchKernelGGL(row_kernel<0>, g, blk, GEMM_LDS, st, p, j, kdone, n_right, n_tiles, syrk);
-        else if (rep == REP_BITS)
-            hipLaunchKernelGGL(row_kernel<1 + REP_BITS>, g, blk, GEMM_LDS, st, p, j, kdone, n_right, n_tiles, syrk);
-        else if (rep == REP_BYTES7)
-            hipLaunchKernelGGL(row_kernel<1 + REP_BYTES7>, g, blk, GEMM_LDS, st, p, j, kdone, n_right, n_tiles, syrk);
-        else
-            hipLaunchKernelGGL(row_kernel<1 + REP_BYTES8>, g, blk, GEMM_LDS, st, p, j, kdone, n_right, n_tiles, syrk);
+        with_gen(sh.fused, rep, [&](auto gen) {
+            hipLaunchKernelGGL(row_kernel<decltype(gen)::value>, dim3(grid), dim3(THREADS), GEMM_LDS, st, p, j, kdone, n_right, n_tiles, syrk);
+        });
         BARK_LAUNCH_CHECK();
         // executed flops: with syrk the partial diagonal tile (present when n_tiles > n_right) takes 36 of 64 sub-block products
         panel_flops += 2.0 * NB * NB * (double)(kdone * NB) * ((double)n_right + (n_tiles > n_right ? (syrk ? 36.0 / 64.0 : 1.0) : 0.0)) * (double)p.Bc;
@@ -502,19 +720,47 @@ struct Sweep {
 
     // rows j and j+1 over k < j in one launch (row_kernel, syrk == 4); j + 1 < nrb
     int launch_row_pair(hipStream_t st, int j) {
-        const int nA = ncb - j - 1, nB = nA - 1, n_sq = nA + nB, n_syrk = 1 + ((j + 2 < nrb) ? 1 : 0);
+        const int nA = sh.ncb - j - 1, nB = nA - 1, n_sq = nA + nB, n_syrk = 1 + ((j + 2 < sh.nrb) ? 1 : 0);
         const unsigned grid = xcd_grid(n_sq, p.Bc) + (unsigned)(n_syrk * NXCD * ((p.Bc + NXCD - 1) / NXCD));
-        const dim3 g(grid), blk(THREADS);
-        if (!fused)
-            hipLaunchKernelGGL(row_kernel<0>, g, blk, GEMM_LDS, st, p, j, j, nA, n_sq, 4);
-        else if (rep == REP_BITS)
-            hipLaunchKernelGGL(row_kernel<1 + REP_BITS>, g, blk, GEMM_LDS, st, p, j, j, nA, n_sq, 4);
-        else if (rep == REP_BYTES7)
-            hipLaunchKernelGGL(row_kernel<1 + REP_BYTES7>, g, blk, GEMM_LDS, st, p, j, j, nA, n_sq, 4);
-        else
-            hipLaunchKernelGGL(row_kernel<1 + REP_BYTES8>, g, blk, GEMM_LDS, st, p, j, j, nA, n_sq, 4);
+        with_gen(sh.fused, rep, [&](auto gen) {
+            hipLaunchKernelGGL(row_kernel<decltype(gen)::value>, dim3(grid), dim3(THREADS), GEMM_LDS, st, p, j, j, nA, n_sq, 4);
+        });
         BARK_LAUNCH_CHECK();
         panel_flops += 2.0 * NB * NB * (double)(j * NB) * ((double)n_sq + n_syrk * 36.0 / 64.0) * (double)p.Bc;
+        return BARK_OK;
+    }
+
+    // solve(j) on the caller's stream: U[j,i] = W_j' T[j,i] for the tiles right of the diagonal; deferred: T lacks the last block
+    // row of its sum, and solve_kernel<1>'s K = 256 product applies it.  Few tiles (the critical path of lone matrices): a tile's
+    // columns shared out over 8 (solve_direct_kernel, not deferred), 4 or 2 workgroups while the launch stays within the
+    // schedule's limit for that form (0: not used)
+    int launch_solve(int j, bool deferred, long direct_max_wgs, long narrow_max_wgs) {
+        const int bc = p.Bc, n_right = sh.ncb - j - 1;
+        if (n_right <= 0) return BARK_OK;
+        int r;
+        if (timed) solve_marks.push_back(ev.size());
+        if ((r = mark_on(main))) return r;
+        const long wgs = (long)n_right * bc;
+        const int parts = (!deferred && wgs * 8 <= direct_max_wgs) ? 8 : wgs * 4 <= narrow_max_wgs ? 4 : wgs * 2 <= narrow_max_wgs ? 2 : 1;
+        const dim3 g(xcd_grid(n_right * parts, bc)), blk(THREADS);
+        if (parts == 8)
+            hipLaunchKernelGGL(solve_direct_kernel<0>, g, blk, 0, main, p, j, n_right);
+        else if (deferred && parts == 4)
+            hipLaunchKernelGGL((solve_narrow_kernel<1, 1>), g, blk, GEMM_LDS, main, p, j, n_right);
+        else if (deferred && parts == 2)
+            hipLaunchKernelGGL((solve_narrow_kernel<2, 1>), g, blk, GEMM_LDS, main, p, j, n_right);
+        else if (deferred)
+            hipLaunchKernelGGL(solve_kernel<1>, g, blk, GEMM_LDS, main, p, j, n_right);
+        else if (parts == 4)
+            hipLaunchKernelGGL((solve_narrow_kernel<1, 0>), g, blk, GEMM_LDS, main, p, j, n_right);
+        else if (parts == 2)
+            hipLaunchKernelGGL((solve_narrow_kernel<2, 0>), g, blk, GEMM_LDS, main, p, j, n_right);
+        else
+            hipLaunchKernelGGL(solve_kernel<0>, g, blk, GEMM_LDS, main, p, j, n_right);
+        BARK_LAUNCH_CHECK();
+        if ((r = mark_on(main))) return r;
+        // 18 of the 32 (k-tile, row-tile) products per wave are executed (zero k-tiles of W_j skipped); deferred: + the dense block
+        solve_flops += ((deferred ? 32.0 : 0.0) + 18.0) / 32.0 * 2.0 * NB * NB * (double)NB * (double)n_right * (double)bc;
         return BARK_OK;
     }
 
@@ -529,10 +775,10 @@ struct Sweep {
     // A last unpaired block row (nrb odd) has no tiles to the right unless there are candidate columns: a plain single launch.
     int step_paired(int j) {
         hipStream_t s = main, ps = panel;
-        const int bc = p.Bc, n_right = ncb - j - 1;
-        const bool even = (j & 1) == 0, pair = even && j + 1 < nrb;
+        const int n_right = sh.ncb - j - 1;
+        const bool even = (j & 1) == 0, pair = even && j + 1 < sh.nrb;
         int r;
-        const bool has_rows = even && (pair || n_right > 0) && (j >= 1 || fused);
+        const bool has_rows = even && (pair || n_right > 0) && (j >= 1 || sh.fused);
         if (has_rows) {
             BARK_HIP_CHECK(hipEventRecord(res->events[6 * j], s));
             if ((r = after(ps, res->events[6 * j]))) return r;
@@ -553,19 +799,7 @@ struct Sweep {
             if ((r = mark_on(ps))) return r;
             if ((r = join(6 * j + 1))) return r;
         }
-        if (n_right > 0) {
-            if (timed) solve_marks.push_back(ev.size());
-            if ((r = mark_on(s))) return r;
-            const dim3 g(xcd_grid(n_right, bc)), blk(THREADS);
-            if (deferred)
-                hipLaunchKernelGGL(solve_kernel<1>, g, blk, GEMM_LDS, s, p, j, n_right);
-            else
-                hipLaunchKernelGGL(solve_kernel<0>, g, blk, GEMM_LDS, s, p, j, n_right);
-            BARK_LAUNCH_CHECK();
-            if ((r = mark_on(s))) return r;
-            solve_flops += ((deferred ? 32.0 : 0.0) + 18.0) / 32.0 * 2.0 * NB * NB * (double)NB * (double)n_right * (double)bc;
-        }
-        return BARK_OK;
+        return launch_solve(j, deferred, 0, 0);
     }
 
     int publish(hipStream_t st, int slot, int value) {
@@ -582,12 +816,11 @@ struct Sweep {
         return BARK_OK;
     }
 
-    // wait_slot: -2 no device-side hand-over; -1 publish the start only; 0 / 1: also wait for that row stream at the end
-    // the whole evaluation of a chunk of one-block-row matrices (N <= 128) in one launch: see OneBlock
-    // N <= 128 with a CU per matrix: the leaf walk runs inside the kernel (OneBlock::nodes) while the points' rows and the forest's
-    // packed nodes fit where the factor image will be
+    // the whole evaluation of a chunk of matrices of one to six block rows (N <= 768) in one launch: see OneBlock.
+    // N <= 128 with a CU per matrix (eight-wave diag_kernel<true>): the leaf walk runs inside the kernel (OneBlock::nodes), no
+    // walk launch, while the points' rows and the forest's packed nodes fit where the factor image will be
     bool walk_in_kernel(const bark_pack_info *sub, int64_t d) const {
-        return BARK_WALK_IN_KERNEL && nrb == 1 && BARK_DIAG_WAVES8 && p.Bc <= DIAG8_MAX_BC &&
+        return sh.nrb == 1 && p.Bc <= DIAG8_MAX_BC &&
                ((size_t)p.N * (d | 1) + 2 + (size_t)sub->m * sub->stride * 2) * sizeof(double) <= (size_t)NBLK * SB * SB * sizeof(double);
     }
     int launch_one_block(const double *y, double *mll, int32_t *fault, int include_2pi, const void *packed_c, const bark_pack_info *sub,
@@ -604,10 +837,10 @@ struct Sweep {
         }
         const size_t lds_bytes = DIAG_LDS + (size_t)p.nW * NB * sizeof(uint32_t);
         // eight waves (factor_tile8) while every matrix of the chunk has a CU to itself; beyond that two four-wave workgroups share one
-        const bool w8 = BARK_DIAG_WAVES8 && p.Bc <= DIAG8_MAX_BC;
-        if (nrb >= 3) {  // multi_block_kernel (256 < N <= 768)
-            hipLaunchKernelGGL(multi_block_kernel, dim3((unsigned)p.Bc), dim3(512), mb_lds_bytes(p.nW, nrb), main, p, ob);
-        } else if (nrb == 2) {  // two_block_kernel: codes of 256 points + z_0 + U_01' z_0 behind the factor image
+        const bool w8 = p.Bc <= DIAG8_MAX_BC;
+        if (sh.nrb >= 3) {  // multi_block_kernel (256 < N <= 768)
+            hipLaunchKernelGGL(multi_block_kernel, dim3((unsigned)p.Bc), dim3(512), mb_lds_bytes(p.nW, sh.nrb), main, p, ob);
+        } else if (sh.nrb == 2) {  // two_block_kernel: codes of 256 points + z_0 + U_01' z_0 behind the factor image
             const size_t lds2 = DIAG_LDS + (size_t)p.nW * 2 * NB * sizeof(uint32_t) + 2 * NB * sizeof(double);
             if (w8)
                 hipLaunchKernelGGL(two_block_kernel<8>, dim3((unsigned)p.Bc), dim3(512), lds2, main, p, ob);
@@ -622,6 +855,7 @@ struct Sweep {
         return BARK_OK;
     }
 
+    // wait_slot: -2 no device-side hand-over; -1 publish the start only; 0 / 1: also wait for that row stream at the end
     int launch_diag(int j, int nkb, int want_g = 0, int wait_slot = -2, int wait_value = 0) {
         int r;
         if (timed) diag_marks.push_back(ev.size());
@@ -631,35 +865,29 @@ struct Sweep {
         // 200-300 us in the middle steps); there it asks for its 83 KiB and lands beside a single bulk workgroup.  (The
         // pipelined schedule's row launches retire workgroups continuously: there the whole-CU request stays the
         // better choice — one N = 16384 matrix 26.6 against 28.3 ms, N = 4096 x 8 4.87 against 5.34.)
-        const bool exclusive = p.Bc <= DIAG_EXCLUSIVE_MAX_BC && !lookahead(j + 1);
+        const bool exclusive = p.Bc <= DIAG_EXCLUSIVE_MAX_BC && !lookahead(sh, p.Bc, j + 1);
         int publish = wait_slot >= -1 ? 1 : 0;
         // chain-bound chunks: the update of the diagonal tile by its block rows above as a launch of its own in front of
         // the one-workgroup kernel (diag_pre_kernel)
-        if (pre_update && nkb > 0) {
+        if (plan.pre_update && nkb > 0) {
             hipLaunchKernelGGL(diag_pre_kernel, dim3(NBLK / (THREADS / 64), (unsigned)p.Bc), dim3(THREADS), 0, main, p, j, nkb, publish);
             BARK_LAUNCH_CHECK();
             nkb = 0;
             publish = 0;
         }
         // the last block step of an MLL-only sweep also writes the MLL (no row launch left to wait for there: wait_slot < 0)
-        const OneBlock fin = (fin_mll && j == nrb_steps - 1 && wait_slot < 0) ? OneBlock{nullptr, fin_mll, fin_fault, fin_2pi, rep} : OneBlock{};
-        if (fin.mll) finished = true;
-        if (exclusive && BARK_DIAG_WAVES8)  // a CU to itself: eight waves (factor_tile8)
+        const OneBlock last = (fin.mll && j == sh.nrb - 1 && wait_slot < 0) ? fin : OneBlock{};
+        if (last.mll) finished = true;
+        if (exclusive)  // a CU to itself: eight waves (factor_tile8)
             hipLaunchKernelGGL((diag_kernel<false, 8>), dim3((unsigned)p.Bc), dim3(512), DIAG_LDS_EXCLUSIVE, main, p, j, nkb, want_g, wait_slot,
-                               wait_value, fin, publish);
+                               wait_value, last, publish);
         else
-            hipLaunchKernelGGL((diag_kernel<false, 4>), dim3((unsigned)p.Bc), dim3(THREADS), exclusive ? DIAG_LDS_EXCLUSIVE : DIAG_LDS, main, p, j, nkb,
-                               want_g, wait_slot, wait_value, fin, publish);
+            hipLaunchKernelGGL((diag_kernel<false, 4>), dim3((unsigned)p.Bc), dim3(THREADS), DIAG_LDS, main, p, j, nkb, want_g, wait_slot,
+                               wait_value, last, publish);
         BARK_LAUNCH_CHECK();
         return mark_on(main);
     }
 
-    // everything enqueued on `main` so far precedes what follows on the panel stream
-    int fork(int slot) {
-        if (panel == main) return BARK_OK;
-        BARK_HIP_CHECK(hipEventRecord(res->events[slot], main));
-        return after(panel, res->events[slot]);
-    }
     // everything enqueued on the panel stream so far precedes what follows on `main`
     int join(int slot) {
         if (panel == main) return BARK_OK;
@@ -669,87 +897,25 @@ struct Sweep {
         return BARK_OK;
     }
 
-    // split-K factor of step j over nkb block rows: fill ~SPLITK_SLOTS workgroup slots, >= 1 block row per slab
-    int split_factor(int j, int nkb, int slots = SPLITK_SLOTS) const {
-        const int n_tiles = (ncb - j - 1) + ((j + 1 < nrb) ? 1 : 0);
-        if (!splitk || j < 1 || n_tiles <= 0 || n_tiles * p.Bc >= SPLITK_SLOTS / 2 || nkb < 1) return 1;
-        int S = slots / (n_tiles * p.Bc);
-        if (slots != SPLITK_SLOTS) {  // look-ahead bulk: aim at `slots` workgroups (nearest S), never more than SPLITK_SLOTS
-            S = (2 * slots + n_tiles * p.Bc) / (2 * n_tiles * p.Bc);
-            while (S > 1 && S * n_tiles * p.Bc > SPLITK_SLOTS) --S;
-        }
-        if (S < 1) S = 1;
-        // a slab on the critical path (the plain split of an under-filled step) may be shorter than a block row: its workgroup is
-        // bound by the latency of its k-tiles' DMA stages (~2.7 us each on an idle chip, 8 per block row), not by their MFMAs
-        int cap = nkb;
-        if (slots == SPLITK_SLOTS && (long)n_tiles * p.Bc * nkb * SPLIT_FINE <= SPLIT_FINE_MAX_WGS) cap = nkb * SPLIT_FINE;  // (see SPLIT_FINE)
-        if (S > cap) S = cap;
-        if (S > SPLITK_MAX) S = SPLITK_MAX;
-        return S;
-    }
-    // look-ahead step: split layout, under-filled, and at least one block row besides the last (j >= 2)
-    // ... and a bulk worth a launch of its own: (tiles x matrices) x block rows >= LA_MIN_WORK, i.e. ~40 us of MFMA
-    // work (4.2 MFLOP per tile and block row); below that the step is bound by diag_kernel and the extra launches and
-    // events only cost (lone N = 4096: 2.88 ms without, 3.11 ms with look-ahead everywhere)
-    bool lookahead(int j) const {
-        if (la_stream == nullptr || j < 2 || j >= nrb_steps || split_factor(j, j) <= 1) return false;
-        const long n_tiles = (ncb - j - 1) + ((j + 1 < nrb) ? 1 : 0);
-        return n_tiles * p.Bc * (long)(j - 1) >= LA_MIN_WORK;
-    }
-    int la_slots(int j) const {  // look-ahead step j: workgroups its bulk (block rows [0, j-1)) aims at
-        const long n_tiles = (ncb - j - 1) + ((j + 1 < nrb) ? 1 : 0);
-        return n_tiles * p.Bc * (long)(j - 1) >= LA_BULK_WORK ? LA_SLOTS : LA_SLOTS_CHAIN;
-    }
     double *slab_set(int j) const { return slabs + (size_t)(j & 1) * SLAB_SET_TILES * NB * NB; }
 
     // split-K over block rows [kb_lo, kb_hi) for the tiles [t_off, t_off + nt) of block row j (nt < 0: all of them)
     int launch_split(hipStream_t st, int j, int kb_lo, int kb_hi, int S, int s_off, int S_tot, int t_off = 0, int nt = -1) {
-        const int n_right = ncb - j - 1, n_all = n_right + ((j + 1 < nrb) ? 1 : 0);
-        if (nt < 0) nt = n_all - t_off;
-        hipLaunchKernelGGL(panel_split_kernel, dim3(xcd_grid(nt * S, p.Bc)), dim3(THREADS), GEMM_LDS, st, p, j, n_right, t_off, nt,
+        if (nt < 0) nt = tiles_of(sh, j) - t_off;
+        hipLaunchKernelGGL(panel_split_kernel, dim3(xcd_grid(nt * S, p.Bc)), dim3(THREADS), GEMM_LDS, st, p, j, sh.ncb - j - 1, t_off, nt,
                            kb_lo, kb_hi, S, s_off, S_tot, slab_set(j));
         BARK_LAUNCH_CHECK();
         panel_flops += 2.0 * NB * NB * (double)((kb_hi - kb_lo) * NB) * (double)nt * (double)p.Bc;
         return BARK_OK;
     }
     int launch_reduce(hipStream_t st, int j, int S_tot, int t_off = 0, int nt = -1) {
-        const int n_right = ncb - j - 1, n_all = n_right + ((j + 1 < nrb) ? 1 : 0);
-        if (nt < 0) nt = n_all - t_off;
+        if (nt < 0) nt = tiles_of(sh, j) - t_off;
         const dim3 g((unsigned)(nt * (NB / RED_ROWS)), (unsigned)p.Bc), blk(THREADS);
-        if (!fused)
-            hipLaunchKernelGGL(panel_reduce_kernel<0>, g, blk, 0, st, p, j, n_right, t_off, nt, S_tot, slab_set(j));
-        else if (rep == REP_BITS)
-            hipLaunchKernelGGL(panel_reduce_kernel<1 + REP_BITS>, g, blk, 0, st, p, j, n_right, t_off, nt, S_tot, slab_set(j));
-        else if (rep == REP_BYTES7)
-            hipLaunchKernelGGL(panel_reduce_kernel<1 + REP_BYTES7>, g, blk, 0, st, p, j, n_right, t_off, nt, S_tot, slab_set(j));
-        else
-            hipLaunchKernelGGL(panel_reduce_kernel<1 + REP_BYTES8>, g, blk, 0, st, p, j, n_right, t_off, nt, S_tot, slab_set(j));
+        with_gen(sh.fused, rep, [&](auto gen) {
+            hipLaunchKernelGGL(panel_reduce_kernel<decltype(gen)::value>, g, blk, 0, st, p, j, sh.ncb - j - 1, t_off, nt, S_tot, slab_set(j));
+        });
         BARK_LAUNCH_CHECK();
         return BARK_OK;
-    }
-    // Ragged last round (chunks that are NOT in the split-K layout): n_tiles x Bc workgroups rarely fill whole rounds
-    // of the chip's SPLITK_SLOTS slots, and the stragglers of the last round run one per CU for a full tile time
-    // (measured at B = 64: up to 35 % per step when one tile in nine is left over).  The tiles beyond the last full
-    // round are split over K instead, so that they finish in a fraction of a round: -> first tile of the tail and its
-    // split factor (tail == n_tiles: nothing to split).
-    void ragged_tail(int j, int n_tiles, int &tail, int &S) const {
-        tail = n_tiles;
-        S = 1;
-        if (splitk || j < 2 || n_tiles <= 0) return;
-        const long bc = p.Bc, slots = SPLITK_SLOTS;
-        const long rounds = (n_tiles * bc) / slots;
-        const long n_plain = rounds * slots / bc;  // tiles that fill whole rounds
-        if (n_plain * bc != rounds * slots) return;  // rounds do not end on a tile boundary (Bc does not divide the slots)
-        const long m = n_tiles - n_plain;
-        // worth it for a sparse last round only (a slab round trip and two more launches): measured at N = 4096,
-        // B = 64 27.8 -> 27.0 ms, B = 48 22.8 -> 21.8 ms; a half-filled last round (B = 256, odd tile counts) gains nothing
-        if (m <= 0 || m * bc > TAIL_MAX_WGS) return;
-        long s = slots / (m * bc);
-        if (s > j) s = j;
-        if (s > SPLITK_MAX) s = SPLITK_MAX;
-        if (s < 3) return;  // a 2-way split of a third-filled round measured slower than leaving it (B = 64, j = 5, 13, 21)
-        tail = (int)n_plain;
-        S = (int)s;
     }
 
     // Block column j of the current chunk (p.Bc matrices): diag(j) || rows(j), then solve(j).  diag(j) and rows(j)
@@ -760,31 +926,30 @@ struct Sweep {
     // bulk (S slabs) is launched on a third stream right after solve(j-2) and runs beside the whole of step j-1; on
     // the critical path of step j remain diag(j) || the rank-128 slab of block row j-1, the reduce and the solve.
     int step(int j) {
-        if (pipelined) return step_pipelined(j);
-        if (paired) return step_paired(j);
+        if (plan.pipelined) return step_pipelined(j);
+        if (plan.paired) return step_paired(j);
         hipStream_t s = main, ps = panel;
         const int bc = p.Bc;
-        const int n_right = ncb - j - 1;
-        const int n_diag = (j + 1 < nrb) ? 1 : 0;
-        const int n_tiles = n_right + n_diag;
+        const int n_right = sh.ncb - j - 1;
+        const int n_tiles = tiles_of(sh, j);
         int r;
-        const bool la = lookahead(j);
-        const int S = la ? split_factor(j, j - 1, la_slots(j)) : split_factor(j, j);
+        const bool la = lookahead(sh, bc, j);
+        const int S = la ? split_factor(sh, bc, j, j - 1, la_slots(sh, bc, j)) : split_factor(sh, bc, j, j);
         // j == 0: with a materialised A the tiles T = A are in place; in fused-Gram sweeps the K = 0 launch writes them
-        const bool has_rows = (j >= 1 || fused) && n_tiles > 0;
+        const bool has_rows = (j >= 1 || sh.fused) && n_tiles > 0;
         // rows(j) on the panel stream and the look-ahead bulk of step j+1 (rows <= j-1 are final) both start once
         // solve(j-1) has retired.  Event form: ONE event recorded after solve(j-1) (every record between two kernels of
         // the caller's stream costs ~3-7 us there).  Device form (dev_wait): nothing on the caller's stream at all —
         // diag_kernel(j) publishes its start in sync[3] and a one-lane gate kernel heads the helper streams' work.
-        const bool bulk_next = lookahead(j + 1);
+        const bool bulk_next = lookahead(sh, bc, j + 1);
         const bool rows_off_stream = has_rows && ps != s;
-        if (dev_gate && j == 0) {  // the helper streams' gates must not read sync before the prologue has zeroed it
+        if (plan.dev_gate && j == 0) {  // the helper streams' gates must not read sync before the prologue has zeroed it
             BARK_HIP_CHECK(hipEventRecord(res->events[5], s));
             if ((r = after(ps, res->events[5])) || (r = after(la_stream, res->events[5])) || (r = after(la_stream2, res->events[5]))) return r;
         }
-        if (!dev_gate && (rows_off_stream || bulk_next)) BARK_HIP_CHECK(hipEventRecord(res->events[6 * j], s));
+        if (!plan.dev_gate && (rows_off_stream || bulk_next)) BARK_HIP_CHECK(hipEventRecord(res->events[6 * j], s));
         if (rows_off_stream) {
-            if (dev_gate) {
+            if (plan.dev_gate) {
                 if ((r = gate(ps, j + 1))) return r;
             } else {
                 if ((r = after(ps, res->events[6 * j]))) return r;
@@ -792,14 +957,14 @@ struct Sweep {
         }
         hipStream_t bulk_next_stream = nullptr;
         if (bulk_next) {
-            const int j2 = j + 1, S2 = split_factor(j2, j2 - 1, la_slots(j2));
+            const int j2 = j + 1, S2 = split_factor(sh, bc, j2, j2 - 1, la_slots(sh, bc, j2));
             // bulk-bound steps alternate between two streams, so that a bulk does not queue behind the last workgroups
             // of its predecessor (one N = 16384 matrix 28.7 -> 28.1 ms, with 10^4 candidates 73.5 -> 69.3); in
             // critical-path-bound steps two resident bulks would only take slots from the critical path
             // (N = 4096, B = 8: 5.04 -> 5.26 ms)
-            hipStream_t ls = ((j2 & 1) && la_slots(j2) == LA_SLOTS) ? la_stream2 : la_stream;
+            hipStream_t ls = ((j2 & 1) && la_slots(sh, bc, j2) == LA_SLOTS) ? la_stream2 : la_stream;
             bulk_next_stream = ls;
-            if (dev_gate) {
+            if (plan.dev_gate) {
                 if ((r = gate(ls, j + 1))) return r;
             } else {
                 if ((r = after(ls, res->events[6 * j]))) return r;
@@ -807,8 +972,8 @@ struct Sweep {
             if ((r = launch_split(ls, j2, 0, j2 - 1, S2, 0, S2 + 1))) return r;
             BARK_HIP_CHECK(hipEventRecord(res->events[6 * j2 + 2], ls));
         }
-        const bool wait_in_diag = dev_wait && rows_off_stream;
-        if ((r = launch_diag(j, j > 0 ? 1 : 0, 0, wait_in_diag ? 0 : (dev_wait ? -1 : -2), j + 1))) return r;
+        const bool wait_in_diag = plan.dev_wait && rows_off_stream;
+        if ((r = launch_diag(j, j > 0 ? 1 : 0, 0, wait_in_diag ? 0 : (plan.dev_wait ? -1 : -2), j + 1))) return r;
         if (has_rows) {
             if (timed) panel_marks.push_back(ev.size());
             if ((r = mark_on(ps))) return r;
@@ -816,7 +981,7 @@ struct Sweep {
                 if ((r = launch_split(ps, j, j - 1, j, 1, S, S + 1))) return r;
                 if ((r = after(ps, res->events[6 * j + 2]))) return r;  // the bulk slabs of step j
                 {  // the stream of bulk(j) is covered by the join of ps below — unless bulk(j + 1) has just gone onto it as well
-                    hipStream_t lsj = ((j & 1) && la_slots(j) == LA_SLOTS) ? la_stream2 : la_stream;
+                    hipStream_t lsj = ((j & 1) && la_slots(sh, bc, j) == LA_SLOTS) ? la_stream2 : la_stream;
                     if (!wait_in_diag && lsj != bulk_next_stream) joined(lsj);
                 }
                 if ((r = launch_reduce(ps, j, S + 1))) return r;
@@ -825,10 +990,11 @@ struct Sweep {
                 if ((r = launch_reduce(ps, j, S))) return r;
             } else {
                 int tail, St;
-                ragged_tail(j, n_tiles, tail, St);
+                ragged_tail(sh, bc, j, tail, St);
                 if (tail > 0) {
-                    const int lockstep = (tail == n_tiles && p.Bc % PLAIN_CHUNK_MULTIPLE == 0) ? BARK_PLAIN_SYRK_MODE : 0;
-                    if ((r = launch_rows(ps, j, j, n_right, tail, lockstep))) {
+                    // lock-step chunks: the SYRK workgroups after all square tiles (see launch_rows)
+                    const int syrk = (tail == n_tiles && plan.lockstep) ? 2 : 0;
+                    if ((r = launch_rows(ps, j, j, n_right, tail, syrk))) {
                         return r;
                     }
                 }
@@ -844,24 +1010,7 @@ struct Sweep {
                 return r;
             }
         }
-        if (n_right > 0) {
-            if (timed) solve_marks.push_back(ev.size());
-            if ((r = mark_on(s))) return r;
-            // few tiles (the critical path of lone matrices): share a tile's columns out over 4 or 2 workgroups
-            if ((long)n_right * bc * 8 <= SOLVE_DIRECT_MAX_WGS)
-                hipLaunchKernelGGL(solve_direct_kernel<0>, dim3(xcd_grid(n_right * 8, bc)), dim3(THREADS), 0, s, p, j, n_right);
-            else if ((long)n_right * bc * 4 <= SOLVE_NARROW_MAX_WGS)
-                hipLaunchKernelGGL(solve_narrow_kernel<1>, dim3(xcd_grid(n_right * 4, bc)), dim3(THREADS), GEMM_LDS, s, p, j, n_right);
-            else if ((long)n_right * bc * 2 <= SOLVE_NARROW_MAX_WGS)
-                hipLaunchKernelGGL(solve_narrow_kernel<2>, dim3(xcd_grid(n_right * 2, bc)), dim3(THREADS), GEMM_LDS, s, p, j, n_right);
-            else
-                hipLaunchKernelGGL(solve_kernel<0>, dim3(xcd_grid(n_right, bc)), dim3(THREADS), GEMM_LDS, s, p, j, n_right);
-            BARK_LAUNCH_CHECK();
-            if ((r = mark_on(s))) return r;
-            // 18 of the 32 (k-tile, row-tile) products per wave are executed (zero k-tiles of W_j skipped)
-            solve_flops += (18.0 / 32.0) * 2.0 * NB * NB * (double)NB * (double)n_right * (double)bc;
-        }
-        return BARK_OK;
+        return launch_solve(j, false, SOLVE_DIRECT_MAX_WGS, SOLVE_NARROW_MAX_WGS);
     }
 
     // ---- pipelined schedule (chunks with enough matrices to fill the chip, i.e. not in the split-K layout) -----------
@@ -873,15 +1022,11 @@ struct Sweep {
     //   caller's stream  diag(j) -> [wait bulk(j)] solve(j) -> diag(j+1) -> ...
     //   helper streams   bulk(j+2) after solve(j)
     // Every bulk launch is awaited on the caller's stream at its own step, so the pattern stays fork/join (capturable).
-    int kdone(int j) const { return j > 0 ? j - 1 : 0; }
-    int tiles_of(int j) const { return (ncb - j - 1) + ((j + 1 < nrb) ? 1 : 0); }
-    // a K = 0 launch only generates A (fused sweeps); with a materialised A there is nothing to do
-    bool has_bulk(int j) const { return j < nrb_steps && tiles_of(j) > 0 && (kdone(j) > 0 || fused); }
     int launch_bulk(int j) {  // everything enqueued on `main` so far precedes it
-        if (!has_bulk(j)) return BARK_OK;
+        if (!has_bulk(sh, j)) return BARK_OK;
         hipStream_t st = (j & 1) ? la_stream : panel;  // one bulk stream only: B = 256 at N = 4096 94 -> 100 ms
         int r;
-        if (dev_gate && j >= 2) {  // called right after solve(j-2): diag_kernel(j-1), next on `main`, publishes j when it starts
+        if (plan.dev_gate && j >= 2) {  // called right after solve(j-2): diag_kernel(j-1), next on `main`, publishes j when it starts
             if ((r = gate(st, j))) return r;
         } else {
             BARK_HIP_CHECK(hipEventRecord(res->events[6 * j + 3], main));
@@ -889,25 +1034,15 @@ struct Sweep {
         }
         if (timed) panel_marks.push_back(ev.size());
         if ((r = mark_on(st))) return r;
-        // the last block rows have few tiles and the longest K: below half a round of workgroups the launch splits K
-        // (slabs + generating reduce, both on the bulk stream, off the critical path; slab sets alternate with j like
-        // the bulk streams).  N = 4096, B = 32: the last 8 steps took 3.5 of 13.9 ms.
-        const int k = kdone(j), nt = tiles_of(j);
-        int S = 1;
-        if (k >= 2 && nt * p.Bc < SPLITK_SLOTS / 2) {
-            S = (2 * PIPE_BULK_SLOTS + nt * p.Bc) / (2 * nt * p.Bc);
-            if (S > k) S = k;
-            if (S > SPLITK_MAX) S = SPLITK_MAX;
-            while (S > 1 && S * nt * p.Bc > SPLITK_SLOTS) --S;
-        }
+        const int k = kdone(j), S = pipe_split(sh, p.Bc, j);
         if (S >= 2) {
             if ((r = launch_split(st, j, 0, k, S, 0, S))) return r;
             if ((r = launch_reduce(st, j, S))) return r;
-        } else if ((r = launch_rows(st, j, k, ncb - j - 1, nt, BARK_PIPE_SYRK_MODE))) {
+        } else if ((r = launch_rows(st, j, k, sh.ncb - j - 1, tiles_of(sh, j), 2))) {  // SYRK workgroups last (see launch_rows)
             return r;
         }
         if ((r = mark_on(st))) return r;
-        if (dev_wait) return publish(st, j & 1, j + 1);  // diag_kernel(j) waits for the counter of this bulk stream
+        if (plan.dev_wait) return publish(st, j & 1, j + 1);  // diag_kernel(j) waits for the counter of this bulk stream
         BARK_HIP_CHECK(hipEventRecord(res->events[6 * j + 2], st));
         return BARK_OK;
     }
@@ -916,10 +1051,9 @@ struct Sweep {
     // looked shorter than diag + solve<1>, but the update launch competes with the resident row launches like the
     // solve does: N = 4096, B = 16 7.27 -> 7.98 ms, one N = 16384 matrix 26.3 -> 27.7.)
     int step_pipelined(int j) {
-        const int bc = p.Bc, n_right = ncb - j - 1;
         int r;
         if (j == 0) {
-            if (dev_gate) {  // the bulk streams' gates must not read sync before the prologue has zeroed it
+            if (plan.dev_gate) {  // the bulk streams' gates must not read sync before the prologue has zeroed it
                 BARK_HIP_CHECK(hipEventRecord(res->events[5], main));
                 if ((r = after(panel, res->events[5])) || (r = after(la_stream, res->events[5]))) return r;
             }
@@ -928,40 +1062,19 @@ struct Sweep {
         }
         // the stored P_jj comes from the row launch of block row j-1: block rows kdone(j-1) .. j-1 are still to apply
         const bool deferred = j > kdone(j);
+        const int n_right = sh.ncb - j - 1;
         // solve(j) (and the next diag) need bulk(j): awaited by event, or — few matrices — inside diag_kernel(j)
-        const bool wait_in_diag = dev_wait && has_bulk(j);
-        if ((r = launch_diag(j, j > 0 ? j - kdone(j - 1) : 0, deferred && n_right > 0, wait_in_diag ? (j & 1) : (dev_wait ? -1 : -2),
+        const bool wait_in_diag = plan.dev_wait && has_bulk(sh, j);
+        if ((r = launch_diag(j, j > 0 ? j - kdone(j - 1) : 0, deferred && n_right > 0, wait_in_diag ? (j & 1) : (plan.dev_wait ? -1 : -2),
                              j + 1)))
             return r;
-        if (has_bulk(j) && !wait_in_diag) {
+        if (has_bulk(sh, j) && !wait_in_diag) {
             BARK_HIP_CHECK(hipStreamWaitEvent(main, res->events[6 * j + 2], 0));
             joined((j & 1) ? la_stream : panel);  // bulk(j)'s stream; bulk(j + 2) touches it again
         }
-        if (n_right > 0) {
-            if (timed) solve_marks.push_back(ev.size());
-            if ((r = mark_on(main))) return r;
-            const long wgs = (long)n_right * bc;
-            const int parts = wgs * 4 <= PIPE_NARROW_MAX_WGS ? 4 : wgs * 2 <= PIPE_NARROW_MAX_WGS ? 2 : 1;
-            const dim3 g(xcd_grid(n_right * parts, bc)), blk(THREADS);
-            if (deferred && parts == 4)
-                hipLaunchKernelGGL((solve_narrow_kernel<1, 1>), g, blk, GEMM_LDS, main, p, j, n_right);
-            else if (deferred && parts == 2)
-                hipLaunchKernelGGL((solve_narrow_kernel<2, 1>), g, blk, GEMM_LDS, main, p, j, n_right);
-            else if (deferred)
-                hipLaunchKernelGGL(solve_kernel<1>, g, blk, GEMM_LDS, main, p, j, n_right);
-            else if (parts == 4)
-                hipLaunchKernelGGL((solve_narrow_kernel<1, 0>), g, blk, GEMM_LDS, main, p, j, n_right);
-            else if (parts == 2)
-                hipLaunchKernelGGL((solve_narrow_kernel<2, 0>), g, blk, GEMM_LDS, main, p, j, n_right);
-            else
-                hipLaunchKernelGGL(solve_kernel<0>, g, blk, GEMM_LDS, main, p, j, n_right);
-            BARK_LAUNCH_CHECK();
-            if ((r = mark_on(main))) return r;
-            solve_flops += ((deferred ? 32.0 : 0.0) + 18.0) / 32.0 * 2.0 * NB * NB * (double)NB * (double)n_right * (double)bc;
-        }
+        if ((r = launch_solve(j, deferred, 0, PIPE_NARROW_MAX_WGS))) return r;
         return launch_bulk(j + 2);
     }
-
     // fill *t from the recorded events (synchronises); [t_begin, t_end] bracket the whole call on `caller`
     int report(bark_mll_timing *t, size_t t_begin, size_t t_end, hipStream_t caller) {
         BARK_HIP_CHECK(hipStreamSynchronize(caller));
@@ -996,82 +1109,6 @@ struct Sweep {
         return BARK_OK;
     }
 };
-
-// Which schedule a chunk of bc resident matrices takes — the ONE place that decides it: bark_mll_batched_hip configures its
-// Sweep from this, and bark_mll_plan_query reports it (DESIGN.md section 4 has the table for the BASELINE configs; a -m gpu
-// test asserts it, so that a tuning constant cannot silently move the headline shape onto another schedule).
-//   sw: splitk / fused / nrb / ncb / nrb_steps / la_stream set; p.Bc is set here (lookahead() reads the chunk size).
-struct ChunkPlan {
-    bool one_block, pipelined, paired, dev_wait, dev_gate, pre_update;
-    int lookahead_steps, splitk_steps;
-};
-ChunkPlan plan_chunk(Sweep &sw, int64_t bc, int64_t C, bool timing, bool dev_wait_ok, bool two_streams) {
-    ChunkPlan c{};
-    const int nrb = sw.nrb;
-    const bool splitk = sw.splitk;
-    // Pipelined schedule: pays whenever the plain schedule leaves ragged rounds of workgroups (measured at N = 4096:
-    // B = 40 +15 %, 64 +7 %, 96 +9 %, 160 +5 %, 192 +4 %; N = 8192, B = 32 +7 %; N = 2048, B = 128..192 +5 %).  When Bc
-    // is a multiple of the 256 CUs every round of the plain schedule is full or exactly half full; the two then tie at
-    // N = 4096 (93.6 | 93.7 ms at B = 256), the plain one wins beyond (B = 512: 186.6 | 188.6; N = 8192, B = 256:
-    // 696 | 711) and the pipelined one up to 16 block rows (N = 2048: 14.1 | 13.8, N = 1024: 2.65 | 2.56).  Fewer than 8
-    // block rows: no difference measured (N = 512..896), plain.
-    const bool pipeline_ok = !splitk && nrb >= PIPE_MIN_NRB;
-    c.pipelined = pipeline_ok && ((bc % PLAIN_CHUNK_MULTIPLE) != 0 || nrb < PLAIN_MIN_NRB);
-    // N <= 128: leaf walk + ONE launch per chunk (OneBlock); 128 < N <= 256: the same with the two-block kernel (two_block_kernel),
-    // while the codes of 256 points fit behind the factor image in LDS (up to 83 code words per point)
-    // ... and while it is the faster form (a workgroup runs its matrix's phases one after the other; the multi-launch sweep spreads a
-    // lone matrix over the chip and overlaps the phases of many): round 5, same box, sweep | two_block_kernel, ms —
-    //   N = 256:  x 1..8 0.103-0.105 | 0.107-0.109 (four waves; with eight waves and the tile generation over all of them 0.098 | 0.088: every
-    //             batch size from 1 on since),  x 256 0.158 | 0.133,  x 512 0.247 | 0.257,  x 1024 0.486 | 0.502,  x 2048 0.88 | 0.96
-    //   N = 200:  x 32 0.105 | 0.097,  x 256 0.156 | 0.118,  x 512 0.245 | 0.227,  x 1024 0.473 | 0.447      N = 144 x 1024  0.468 | 0.400
-    const bool two_ok = nrb == 2 && DIAG_LDS + (size_t)sw.p.nW * 2 * NB * sizeof(uint32_t) + 2 * NB * sizeof(double) <= DIAG_LDS_EXCLUSIVE &&
-                        bc >= TWO_MIN_BC && (bc <= TWO_MAX_BC || sw.p.N <= TWO_ANY_BC_MAX_N);
-    c.one_block = (nrb == 1 || (BARK_TWO_BLOCK && two_ok)) && sw.fused && C == 0 && !timing;
-    // 256 < N <= 768: multi_block_kernel (three to six block rows in one launch, eight waves), whatever layout the sweep would
-    // take for the chunk, while the codes of the matrix's points fit beside the factor image and the GEMM stages in LDS
-    if (BARK_MULTI_BLOCK && nrb >= 3 && nrb <= MB_MAX_NRB && C == 0 && !timing && mb_chunk_ok(nrb, bc) &&
-        mb_lds_bytes(sw.p.nW, nrb) <= DIAG_LDS_EXCLUSIVE)
-        c.one_block = true;
-    sw.p.Bc = (int)bc;  // lookahead() / split_factor() read the chunk size
-    if (c.one_block) {
-        c.pipelined = false;
-        return c;
-    }
-    c.paired = BARK_PLAIN_PAIRS && !c.pipelined && !splitk && nrb >= PLAIN_MIN_NRB && bc % PLAIN_CHUNK_MULTIPLE == 0 && two_streams;
-    c.dev_wait = dev_wait_ok && (splitk || c.pipelined) && bc <= DEVWAIT_MAX_BC;
-    // gate kernels in place of the event record that releases the row streams: measured (one process per variant,
-    // gates | end-of-diag wait only | events, ms): pipelined N = 4096 x 8 4.44 | 4.59 | 4.64, N = 8192 x 2 8.18 | 8.35 |
-    // 8.48; split-K layout N = 4096 x 1 2.19 | 2.14 | 2.22, N = 1024 x 1 0.575 | 0.520 | 0.534 — pipelined only
-    // ... split-K layout: only for sweeps with look-ahead steps (N = 6900 x 1 5.02 -> 4.59 with gates; without look-ahead
-    // they cost: N = 4096 x 1 2.04 -> 2.28, N = 2048 x 4 1.09 -> 1.21)
-    c.dev_gate = c.dev_wait && c.pipelined;
-    if (!c.pipelined && !c.paired) {
-        for (int jj = 1; jj < nrb; ++jj) {
-            const bool la = sw.lookahead(jj);
-            c.lookahead_steps += la ? 1 : 0;
-            c.splitk_steps += (la || sw.split_factor(jj, jj) > 1) ? 1 : 0;
-        }
-        if (c.dev_wait && c.lookahead_steps > 0) c.dev_gate = true;
-    } else if (c.pipelined) {
-        for (int jj = 0; jj < nrb; ++jj) {
-            const int k = sw.kdone(jj), nt = sw.tiles_of(jj);
-            if (sw.has_bulk(jj) && k >= 2 && nt * (int)bc < SPLITK_SLOTS / 2 && (2 * PIPE_BULK_SLOTS + nt * (int)bc) / (2 * nt * (int)bc) >= 2)
-                ++c.splitk_steps;
-        }
-    }
-    // split-K layout only: same box, this | inside diag_kernel, ms — N = 4096 x 1 2.035 | 2.130, N = 1024 x 1 0.492 | 0.514,
-    // N = 2048 x 4 1.082 | 1.125; in the pipelined schedule the extra launch queues for slots behind the resident row
-    // workgroups like every kernel of the chain does (N = 4096 x 8 4.77 | 4.46, x 16 7.61 | 7.11, N = 16384 x 1 27.2 | 25.4)
-    c.pre_update = splitk && bc <= DEVWAIT_MAX_BC;
-    return c;
-}
-int plan_code(const ChunkPlan &c, bool splitk, int nrb) {
-    if (c.one_block) return nrb >= 3 ? BARK_SCHED_MULTI_BLOCK : nrb == 2 ? BARK_SCHED_TWO_BLOCK : BARK_SCHED_ONE_BLOCK;
-    if (c.paired) return BARK_SCHED_PAIRED;
-    if (c.pipelined) return BARK_SCHED_PIPELINED;
-    if (splitk) return c.lookahead_steps > 0 ? BARK_SCHED_SPLITK_LOOKAHEAD : BARK_SCHED_SPLITK;
-    return BARK_SCHED_PLAIN;
-}
 
 }  // namespace
 }  // namespace bark
@@ -1124,33 +1161,25 @@ int bark_mll_plan_query(int64_t N, int64_t C, int64_t m, int64_t B, int64_t Bc, 
         return fail(BARK_ERR_ARG, "bark_mll_plan_query: bad argument");
     if (Bc > B) Bc = B;
     if (Bc > 65535) Bc = 65535;
-    const Layout L = make_layout(N, C, m, Bc);
-    Sweep sw;
-    sw.nrb = sw.nrb_steps = (int)(L.npad / NB);
-    sw.ncb = (int)(L.ncols / NB);
-    sw.splitk = L.splitk;
-    sw.fused = !L.splitk && C == 0 && (size_t)2 * leaf_words * NB * sizeof(uint32_t) <= GEMM_LDS;
-    sw.la_stream = sw.la_stream2 = reinterpret_cast<hipStream_t>(&sw);  // non-null: look-ahead possible (never dereferenced)
-    sw.p.nW = leaf_words;
-    sw.p.N = (int)N;
+    const SweepShape sh = make_shape(make_layout(N, C, m, Bc), N, leaf_words);
     const bool dw = device_wait_enabled().load();
     const int64_t last = B % Bc ? B % Bc : Bc;
-    const ChunkPlan lastp = plan_chunk(sw, last, C, timing != 0, dw, true);
-    const ChunkPlan first = plan_chunk(sw, Bc, C, timing != 0, dw, true);
+    const ChunkPlan first = plan_chunk(sh, Bc, timing != 0, dw, true, SweepPath::Dense);
+    const ChunkPlan lastp = plan_chunk(sh, last, timing != 0, dw, true, SweepPath::Dense);
     out->n_chunks = (int32_t)((B + Bc - 1) / Bc);
     out->chunk = (int32_t)Bc;
     out->last_chunk = (int32_t)last;
-    out->schedule = plan_code(first, L.splitk, sw.nrb);
-    out->last_schedule = plan_code(lastp, L.splitk, sw.nrb);
-    out->splitk_layout = L.splitk ? 1 : 0;
-    out->fused_gram = sw.fused ? 1 : 0;
+    out->schedule = plan_code(first, sh);
+    out->last_schedule = plan_code(lastp, sh);
+    out->splitk_layout = sh.splitk ? 1 : 0;
+    out->fused_gram = sh.fused ? 1 : 0;
     out->dev_wait = first.dev_wait ? 1 : 0;
     out->dev_gate = first.dev_gate ? 1 : 0;
     out->pre_update = first.pre_update ? 1 : 0;
     out->lookahead_steps = first.lookahead_steps;
     out->splitk_steps = first.splitk_steps;
-    out->nrb = sw.nrb;
-    out->ncb = sw.ncb;
+    out->nrb = sh.nrb;
+    out->ncb = sh.ncb;
     return BARK_OK;
 }
 
@@ -1189,65 +1218,34 @@ int bark_mll_batched_hip(bark_ctx *ctx, const void *packed, const bark_pack_info
     const int words = (int)bark_leaf_words(info);
     if (words > MAX_LEAF_WORDS) return fail(BARK_ERR_ARG, "forest needs %d leaf-code words per point (max %d)", words, MAX_LEAF_WORDS);
     const bool use_scale = (flags & BARK_MLL_INCLUDE_SCALE) != 0;
-    // MLL-only sweeps generate A inside the row kernels; only the tile (0, 0) is materialised (input of diag(0)).
-    // With candidates (or split-K) the whole matrix is filled up front.
-    const bool splitk = L.splitk;  // then A is materialised (the reduce kernel reads it)
-    const bool fused = !splitk && C == 0 && (size_t)2 * words * NB * sizeof(uint32_t) <= GEMM_LDS;
-    double *slabs = reinterpret_cast<double *>(static_cast<char *>(workspace) + L.off_slab);
-    const int nrb = (int)(L.npad / NB), ncb = (int)(L.ncols / NB);
-    if ((rc = ctx_events(ctx, (size_t)6 * nrb + 6))) return rc;
+    const int two_pi = (flags & BARK_MLL_INCLUDE_2PI) ? 1 : 0;
+    const SweepShape sh = make_shape(L, N, words);
+    if ((rc = ctx_events(ctx, (size_t)6 * sh.nrb + 6))) return rc;
+    Sweep sw(ctx, caller, L, workspace, sh, (int)m, rep, timing != nullptr);
+    uint32_t *leafx = reinterpret_cast<uint32_t *>(static_cast<char *>(workspace) + L.off_leafx);
+    uint32_t *leafc = reinterpret_cast<uint32_t *>(static_cast<char *>(workspace) + L.off_leafc);
 
-    Sweep sw;
-    sw.res = ctx;
-    sw.nrb = nrb;
-    sw.nrb_steps = nrb;
-    sw.la_stream = ctx->helper2;
-    sw.la_stream2 = ctx->helper3;
-    sw.ncb = ncb;
-    sw.fused = fused;
-    sw.splitk = splitk;
-    sw.rep = rep;
-    sw.slabs = slabs;
-    sw.timed = timing != nullptr;
-    sw.main = caller;
-    sw.panel = ctx->helper;
-    uint32_t *leafx, *leafc;
-    {
-        char *ws = static_cast<char *>(workspace);
+    // the chunk's forests and per-forest parameters (p.Bc: configure); -> its packed forests
+    auto bind_chunk = [&](int64_t c0) -> const char * {
         Mats &p = sw.p;
-        p.A = reinterpret_cast<double *>(ws + L.off_A);
-        p.ld = L.ld;
-        p.bstride = L.npad * L.ld;
-        p.W = reinterpret_cast<double *>(ws + L.off_W);
-        p.yz = reinterpret_cast<double *>(ws + L.off_yz);
-        p.accum = reinterpret_cast<double *>(ws + L.off_acc);
-        p.sync = reinterpret_cast<int32_t *>(ws + L.off_sync);
-        p.nrb = nrb;
-        p.ncb = ncb;
-        p.nW = words;
-        p.m = (int)m;
-        p.N = (int)N;
-        leafx = reinterpret_cast<uint32_t *>(ws + L.off_leafx);
-        leafc = reinterpret_cast<uint32_t *>(ws + L.off_leafc);
-    }
+        p.info = info_out + c0;
+        p.leafx = (sh.fused || sw.plan.one_block) ? leafx : nullptr;  // (the kernels that generate A from the codes)
+        p.scale = use_scale ? scale + c0 : nullptr;
+        p.shift = shift ? shift + c0 : nullptr;
+        p.noise = noise + c0;
+        return static_cast<const char *>(packed) + (size_t)c0 * m * info->stride * 16;
+    };
 
-    auto prologue = [&](int64_t c0, int64_t bc) -> int {  // leaf walk, Gram fill, right-hand sides of one chunk
+    auto prologue = [&](const char *packed_c, int64_t bc) -> int {  // leaf walk, Gram fill, right-hand sides of one chunk
         Mats &p = sw.p;
         hipStream_t s = sw.main;
         bark_pack_info sub = *info;
         sub.B = bc;
-        const char *packed_c = static_cast<const char *>(packed) + (size_t)c0 * m * info->stride * 16;
-        p.info = info_out + c0;
-        p.Bc = (int)bc;
-        p.leafx = fused ? leafx : nullptr;
-        p.scale = use_scale ? scale + c0 : nullptr;
-        p.shift = shift ? shift + c0 : nullptr;
-        p.noise = noise + c0;
         int r;
         if (sw.timed) sw.gram_marks.push_back(sw.ev.size());
         if ((r = sw.mark_on(s))) return r;
         if ((r = walk_codes(packed_c, &sub, X, N, d, leafx, ctx->fault, s))) return r;
-        const int fill = fused ? NB : (int)L.npad;
+        const int fill = sh.fused ? NB : (int)L.npad;
         r = launch_gram(leafx, (int)L.npad, leafx, (int)L.npad, bc, m, (int)N, (int)N, fill, fill,
                         p.shift, p.scale, p.noise, p.A, L.ld, p.bstride, true, true, rep, words, s);
         if (r) return r;
@@ -1258,7 +1256,7 @@ int bark_mll_batched_hip(bark_ctx *ctx, const void *packed, const bark_pack_info
         } else if (C > 0) {
             if ((r = walk_codes(packed_c, &sub, cand, C, d, leafc, ctx->fault, s))) return r;
             r = launch_gram(leafx, (int)L.npad, leafc, (int)L.cpad, bc, m, (int)N, (int)C, (int)L.npad,
-                            (int)L.cpad, p.shift, scale + c0, nullptr, p.A + L.npad, L.ld, p.bstride, false, false, rep, words, s);
+                            (int)L.cpad, p.shift, p.scale, nullptr, p.A + L.npad, L.ld, p.bstride, false, false, rep, words, s);
             if (r) return r;
         }
         dim3 g((unsigned)((L.npad + 255) / 256), (unsigned)bc);
@@ -1266,13 +1264,12 @@ int bark_mll_batched_hip(bark_ctx *ctx, const void *packed, const bark_pack_info
         BARK_LAUNCH_CHECK();
         return sw.mark_on(s);
     };
-
     auto epilogue = [&](int64_t c0, int64_t bc) -> int {  // MLL and posterior reductions of one chunk
         Mats &p = sw.p;
         hipStream_t s = sw.main;
         if (!sw.finished) {
             hipLaunchKernelGGL(finish_mll_kernel, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, s, p.accum, (int)bc, (int)N,
-                               (flags & BARK_MLL_INCLUDE_2PI) ? 1 : 0, mll_out + c0, ctx->fault, p.info, sw.dev_wait ? p.sync : nullptr);
+                               two_pi, mll_out + c0, ctx->fault, p.info, sw.plan.dev_wait ? p.sync : nullptr);
             BARK_LAUNCH_CHECK();
         }
         if (C > 0) {
@@ -1301,57 +1298,21 @@ int bark_mll_batched_hip(bark_ctx *ctx, const void *packed, const bark_pack_info
     }
     const size_t t_begin = sw.ev.size();
     if ((rc = sw.mark_on(caller))) return rc;
-    auto chunks = [&]() -> int {
-    for (int64_t c0 = 0; c0 < B; c0 += Bc) {  // chunks of Bc resident matrices, one after the other
-        const int64_t bc = (B - c0 < Bc) ? (B - c0) : Bc;
-        const ChunkPlan plan = plan_chunk(sw, bc, C, timing != nullptr, dev_wait_ok, sw.panel != sw.main);  // (sets sw.p.Bc)
-        sw.pipelined = plan.pipelined;
-        if (plan.one_block) {  // N <= 128: leaf walk + ONE launch per chunk (OneBlock)
-            Mats &p1 = sw.p;
+    rc = sw.for_chunks(B, Bc, [&](int64_t c0, int64_t bc) -> int {
+        sw.configure(plan_chunk(sh, bc, timing != nullptr, dev_wait_ok, sw.panel != sw.main, SweepPath::Dense), bc,
+                     (C == 0 && !timing) ? OneBlock{nullptr, mll_out + c0, ctx->fault, two_pi, rep} : OneBlock{});
+        const char *packed_c = bind_chunk(c0);
+        int r;
+        if (sw.plan.one_block) {  // leaf walk + ONE launch per chunk (OneBlock)
             bark_pack_info sub = *info;
             sub.B = bc;
-            p1.info = info_out + c0;
-            p1.Bc = (int)bc;
-            p1.leafx = leafx;
-            p1.scale = use_scale ? scale + c0 : nullptr;
-            p1.shift = shift ? shift + c0 : nullptr;
-            p1.noise = noise + c0;
-            const char *packed_c = static_cast<const char *>(packed) + (size_t)c0 * m * info->stride * 16;
-            if (!sw.walk_in_kernel(&sub, d) && (rc = walk_codes(packed_c, &sub, X, N, d, leafx, ctx->fault, caller))) return rc;
-            if ((rc = sw.launch_one_block(y, mll_out + c0, ctx->fault, (flags & BARK_MLL_INCLUDE_2PI) ? 1 : 0, packed_c, &sub, X, d))) return rc;
-            continue;
+            if (!sw.walk_in_kernel(&sub, d) && (r = walk_codes(packed_c, &sub, X, N, d, leafx, ctx->fault, caller))) return r;
+            return sw.launch_one_block(y, mll_out + c0, ctx->fault, two_pi, packed_c, &sub, X, d);
         }
-        sw.paired = plan.paired;
-        sw.dev_wait = plan.dev_wait;
-        sw.dev_gate = plan.dev_gate;
-        sw.pre_update = plan.pre_update;
-        sw.finished = false;
-        sw.fin_mll = (C == 0 && !timing) ? mll_out + c0 : nullptr;
-        sw.fin_fault = ctx->fault;
-        sw.fin_2pi = (flags & BARK_MLL_INCLUDE_2PI) ? 1 : 0;
-        if ((rc = prologue(c0, bc))) return rc;
-        for (int j = 0; j < nrb; ++j)
-            if ((rc = sw.step(j))) return rc;
-        // device-side hand-over: nothing has joined the helper streams to the caller's yet (the last diag_kernel waited for
-        // their counters; after a time-out it did not).  One event join per touched stream and chunk, so that neither the next
-        // chunk's prologue nor the caller's next use of the workspace can overtake a row launch of this one.
-        if (sw.dev_wait) sw.rejoin_helpers();
-        if ((rc = epilogue(c0, bc))) return rc;
-    }
-    return BARK_OK;
-    };
-    rc = chunks();
-    if (rc) {  // an error return from the middle of a chunk: helper streams may be forked (under capture: unjoined)
-        // a gate kernel of a helper stream may be waiting for a diag_kernel that will now never be launched: raise the sticky
-        // time-out word first, so that it gives up at once instead of holding the rejoin for its 2 s bound (best effort)
-        if (sw.dev_gate && sw.p.sync) {
-            hipLaunchKernelGGL(sync_publish_kernel, dim3(1), dim3(1), 0, caller, sw.p.sync, 2, 1);
-            (void)hipGetLastError();
-        }
-        sw.rejoin_helpers();
-        return rc;
-    }
-    sw.rejoin_helpers();  // whatever is still marked touched (Sweep::joined clears a stream's mark when an event join covers it)
+        if ((r = prologue(packed_c, bc)) || (r = sw.factor())) return r;
+        return epilogue(c0, bc);
+    });
+    if (rc) return rc;
     const size_t t_end = sw.ev.size();
     if ((rc = sw.mark_on(caller))) return rc;
     if (timing) return sw.report(timing, t_begin, t_end, caller);
@@ -1465,38 +1426,13 @@ static int leafspace_run(bark_ctx *ctx, const void *packed, const bark_pack_info
     if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(BARK_ERR_ARG, "workspace must be 256-byte aligned");
     if ((rc = set_lds_limits())) return rc;
     hipStream_t caller = static_cast<hipStream_t>(stream_);
-    const int nrb = (int)(g.Rpad / NB);
-    if ((rc = ctx_events(ctx, (size_t)6 * nrb + 6))) return rc;
-
-    char *ws = static_cast<char *>(workspace);
-    const int ncb = (int)(g.L.ncols / NB);  // posterior: R identity columns appended (M^-1 and w = M^-1 v)
-    Sweep sw;
-    sw.res = ctx;
-    sw.nrb = nrb;
-    sw.nrb_steps = nrb;
-    sw.la_stream = ctx->helper2;
-    sw.la_stream2 = ctx->helper3;
-    sw.ncb = ncb;
-    sw.fused = false;
-    sw.splitk = g.L.splitk;
-    sw.slabs = reinterpret_cast<double *>(ws + g.L.off_slab);
-    sw.main = caller;
-    sw.panel = ctx->helper;
+    // the R x R sweep: N := R points, no leaf codes (A is filled by leafspace_prepare); posterior / inverse: R identity columns
+    // appended (M^-1 and w = M^-1 v)
+    const SweepShape sh = make_shape(g.L, g.R, 0);
+    if ((rc = ctx_events(ctx, (size_t)6 * sh.nrb + 6))) return rc;
+    Sweep sw(ctx, caller, g.L, workspace, sh, (int)m);
     Mats &p = sw.p;
-    p.A = reinterpret_cast<double *>(ws + g.L.off_A);
-    p.ld = g.L.ld;
-    p.bstride = g.L.npad * g.L.ld;
-    p.W = reinterpret_cast<double *>(ws + g.L.off_W);
-    p.yz = reinterpret_cast<double *>(ws + g.L.off_yz);
-    p.accum = reinterpret_cast<double *>(ws + g.L.off_acc);
-    p.sync = nullptr;  // R x R systems: a block row or two, event joins are fine (sw.dev_wait stays false)
-    p.nrb = nrb;
-    p.ncb = ncb;
-    p.leafx = nullptr;
-    p.scale = p.shift = p.noise = nullptr;
-    p.nW = 0;
-    p.m = (int)m;
-    p.N = (int)g.R;
+    char *ws = static_cast<char *>(workspace);
     uint32_t *codes = reinterpret_cast<uint32_t *>(ws + g.off_codes);
     unsigned long long *planes = reinterpret_cast<unsigned long long *>(ws + g.off_planes);
     double *yy = reinterpret_cast<double *>(ws + g.off_yy);
@@ -1506,15 +1442,12 @@ static int leafspace_run(bark_ctx *ctx, const void *packed, const bark_pack_info
     const bool use_scale = (flags & BARK_MLL_INCLUDE_SCALE) != 0;
 
     if ((rc = leafspace_sumsq(y, (int)N, yy, caller))) return rc;
-    auto chunks = [&]() -> int {
-    for (int64_t c0 = 0; c0 < B; c0 += Bc) {
-        const int64_t bc = (B - c0 < Bc) ? (B - c0) : Bc;
+    return sw.for_chunks(B, Bc, [&](int64_t c0, int64_t bc) -> int {
         bark_pack_info sub = *info;
         sub.B = bc;
         const char *packed_c = static_cast<const char *>(packed) + (size_t)c0 * m * info->stride * 16;
+        sw.configure(plan_chunk(sh, bc, false, false, sw.panel != sw.main, SweepPath::LeafSpace), bc);
         p.info = info_out + c0;
-        p.Bc = (int)bc;
-        sw.pipelined = !g.L.splitk && nrb >= PIPE_MIN_NRB && ((bc % PLAIN_CHUNK_MULTIPLE) != 0 || nrb < PLAIN_MIN_NRB);  // plan_chunk's rule
         if ((rc = walk_one_hot(packed_c, &sub, X, N, d, (int)g.W, codes, ctx->fault, caller))) return rc;
         rc = leafspace_prepare(codes, (int)g.W, (int)g.npad, planes, (int)g.R, (int)g.Rpad, noise + c0,
                                use_scale ? scale + c0 : nullptr, (int)m, (int)bc, p.A, p.ld, p.bstride, y, (int)N, p.yz,
@@ -1525,8 +1458,7 @@ static int leafspace_run(bark_ctx *ctx, const void *packed, const bark_pack_info
             hipLaunchKernelGGL(identity_rhs_kernel, gi, dim3(256), 0, caller, p, (int)g.R, (int)g.L.cpad);
             BARK_LAUNCH_CHECK();
         }
-        for (int j = 0; j < nrb; ++j)
-            if ((rc = sw.step(j))) return rc;
+        if ((rc = sw.factor())) return rc;
         if (mll_out) {
             rc = leafspace_finish(p.accum, yy, noise + c0, use_scale ? scale + c0 : nullptr, (int)m, (int)bc, (int)N,
                                   (flags & BARK_MLL_INCLUDE_2PI) ? 1 : 0, mll_out + c0, caller);
@@ -1539,7 +1471,7 @@ static int leafspace_run(bark_ctx *ctx, const void *packed, const bark_pack_info
                 return rc;
             if ((rc = walk_one_hot(packed_c, &sub, cand, C, d, (int)g.W, ccodes, ctx->fault, caller))) return rc;
             double *Wt = reinterpret_cast<double *>(ws + g.off_wt);
-            rc = sample_weights(p.A + (size_t)nrb * NB, p.ld, p.bstride, wvec, draws.eps + (size_t)c0 * S * R, R, (int)g.Rpad, S,
+            rc = sample_weights(p.A + (size_t)sh.nrb * NB, p.ld, p.bstride, wvec, draws.eps + (size_t)c0 * S * R, R, (int)g.Rpad, S,
                                 (int)g.Spad, noise + c0, scale + c0, (int)m, (int)bc, Wt, caller);
             if (rc) return rc;
             const bool full = draws.reduce == BARK_SAMPLE_FULL;
@@ -1575,12 +1507,8 @@ static int leafspace_run(bark_ctx *ctx, const void *packed, const bark_pack_info
         hipLaunchKernelGGL(fault_info_kernel, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, caller, ctx->fault, p.info,
                            (int)bc);
         BARK_LAUNCH_CHECK();
-    }
-    return BARK_OK;
-    };
-    rc = chunks();
-    sw.rejoin_helpers();  // also on an error return from the middle of a sweep: no helper stream stays forked
-    return rc;
+        return BARK_OK;
+    });
 }
 
 extern "C" {

@@ -384,3 +384,163 @@ def test_schedule_table_of_the_baseline_configs():
         assert schedule_plan(1024, 1)["dev_wait"] == 0 and schedule_plan(4096, 8)["dev_gate"] == 0
     finally:
         _lib.lib().bark_device_wait(prev)
+
+
+# Every field of bark_mll_plan for shapes on both sides of each threshold plan_chunk reads: every row of DESIGN.md section 4's
+# table, PIPE_MIN_NRB / PLAIN_MIN_NRB (N = 896 | 897, 1920 | 1921), PLAIN_CHUNK_MULTIPLE, DEVWAIT_MAX_BC (32 | 33), TWO_MAX_BC /
+# TWO_ANY_BC_MAX_N (384 | 385, N = 224 | 225), MB_MIN_BC3 / 4 / 5 (80, 112, 144), the 70 % / 80 % round rules (359, 538 / 410),
+# the leaf-word limits of the one-launch kernels (83 at two block rows; 15 / 11 / 7 / 6 at three to six), SPLITK_LAYOUT_MAX_TILES /
+# MAX_WORK, LA_MIN_WORK, candidates, timing, the device-side wait switched off, ragged last chunks.
+# (N, B, C, chunk, leaf_words, timing, device wait) -> the fields in PLAN_FIELDS order
+PLAN_FIELDS = ("n_chunks", "chunk", "last_chunk", "schedule", "last_schedule", "splitk_layout", "fused_gram", "dev_wait", "dev_gate",
+               "pre_update", "lookahead_steps", "splitk_steps", "nrb", "ncb")
+PLAN_TABLE = {
+    (64, 1, 0, None, 5, 0, 1): (1, 1, 1, "one_block", "one_block", 0, 1, 0, 0, 0, 0, 0, 1, 1),
+    (1024, 1, 0, None, 5, 0, 1): (1, 1, 1, "splitk", "splitk", 1, 0, 1, 0, 1, 0, 6, 8, 8),
+    (4096, 256, 0, None, 5, 0, 1): (1, 256, 256, "paired", "paired", 0, 1, 0, 0, 0, 0, 0, 32, 32),
+    (4096, 64, 0, None, 5, 0, 1): (1, 64, 64, "pipelined", "pipelined", 0, 1, 0, 0, 0, 0, 2, 32, 32),
+    (4096, 512, 0, 256, 5, 0, 1): (2, 256, 256, "paired", "paired", 0, 1, 0, 0, 0, 0, 0, 32, 32),
+    (16384, 1, 0, None, 5, 0, 1): (1, 1, 1, "pipelined", "pipelined", 0, 1, 1, 1, 0, 0, 124, 128, 128),
+    (16384, 1, 10000, None, 5, 0, 1): (1, 1, 1, "pipelined", "pipelined", 0, 0, 1, 1, 0, 0, 125, 128, 207),
+    (16384, 4, 0, None, 5, 0, 1): (1, 4, 4, "pipelined", "pipelined", 0, 1, 1, 1, 0, 0, 62, 128, 128),
+    (4096, 1, 0, None, 5, 0, 1): (1, 1, 1, "splitk", "splitk", 1, 0, 1, 0, 1, 0, 30, 32, 32),
+    (4096, 8, 0, None, 5, 0, 1): (1, 8, 8, "pipelined", "pipelined", 0, 1, 1, 1, 0, 0, 28, 32, 32),
+    (4096, 16, 0, None, 5, 0, 1): (1, 16, 16, "pipelined", "pipelined", 0, 1, 1, 1, 0, 0, 14, 32, 32),
+    (64, 256, 0, None, 5, 0, 1): (1, 256, 256, "one_block", "one_block", 0, 1, 0, 0, 0, 0, 0, 1, 1),
+    (256, 256, 0, None, 5, 0, 1): (1, 256, 256, "two_block", "two_block", 0, 1, 0, 0, 0, 0, 0, 2, 2),
+    (512, 256, 0, None, 5, 0, 1): (1, 256, 256, "multi_block", "multi_block", 0, 1, 0, 0, 0, 0, 0, 4, 4),
+    (384, 512, 0, None, 5, 0, 1): (1, 512, 512, "multi_block", "multi_block", 0, 1, 0, 0, 0, 0, 0, 3, 3),
+    (384, 64, 0, None, 5, 0, 1): (1, 64, 64, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 3, 3),
+    (768, 256, 0, None, 5, 0, 1): (1, 256, 256, "multi_block", "multi_block", 0, 1, 0, 0, 0, 0, 0, 6, 6),
+    (768, 384, 0, None, 5, 0, 1): (1, 384, 384, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 6, 6),
+    (512, 64, 0, None, 5, 0, 1): (1, 64, 64, "splitk", "splitk", 1, 0, 0, 0, 0, 0, 1, 4, 4),
+    (2048, 256, 0, None, 5, 0, 1): (1, 256, 256, "paired", "paired", 0, 1, 0, 0, 0, 0, 0, 16, 16),
+    (6900, 1, 0, None, 5, 0, 1): (1, 1, 1, "splitk_lookahead", "splitk_lookahead", 1, 0, 1, 1, 1, 32, 52, 54, 54),
+    (896, 100, 0, None, 5, 0, 1): (1, 100, 100, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 7, 7),
+    (897, 100, 0, None, 5, 0, 1): (1, 100, 100, "pipelined", "pipelined", 0, 1, 0, 0, 0, 0, 1, 8, 8),
+    (1024, 100, 0, None, 5, 0, 1): (1, 100, 100, "pipelined", "pipelined", 0, 1, 0, 0, 0, 0, 1, 8, 8),
+    (896, 256, 0, None, 5, 0, 1): (1, 256, 256, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 7, 7),
+    (1024, 256, 0, None, 5, 0, 1): (1, 256, 256, "pipelined", "pipelined", 0, 1, 0, 0, 0, 0, 0, 8, 8),
+    (1920, 256, 0, None, 5, 0, 1): (1, 256, 256, "pipelined", "pipelined", 0, 1, 0, 0, 0, 0, 0, 15, 15),
+    (1921, 256, 0, None, 5, 0, 1): (1, 256, 256, "paired", "paired", 0, 1, 0, 0, 0, 0, 0, 16, 16),
+    (1920, 512, 0, None, 5, 0, 1): (1, 512, 512, "pipelined", "pipelined", 0, 1, 0, 0, 0, 0, 0, 15, 15),
+    (1921, 512, 0, None, 5, 0, 1): (1, 512, 512, "paired", "paired", 0, 1, 0, 0, 0, 0, 0, 16, 16),
+    (4096, 255, 0, None, 5, 0, 1): (1, 255, 255, "pipelined", "pipelined", 0, 1, 0, 0, 0, 0, 0, 32, 32),
+    (4096, 257, 0, None, 5, 0, 1): (1, 257, 257, "pipelined", "pipelined", 0, 1, 0, 0, 0, 0, 0, 32, 32),
+    (4096, 512, 0, None, 5, 0, 1): (1, 512, 512, "paired", "paired", 0, 1, 0, 0, 0, 0, 0, 32, 32),
+    (4096, 768, 0, None, 5, 0, 1): (1, 768, 768, "paired", "paired", 0, 1, 0, 0, 0, 0, 0, 32, 32),
+    (4096, 512, 0, 255, 5, 0, 1): (3, 255, 2, "pipelined", "pipelined", 0, 1, 0, 0, 0, 0, 0, 32, 32),
+    (2048, 1000, 0, 256, 5, 0, 1): (4, 256, 232, "paired", "pipelined", 0, 1, 0, 0, 0, 0, 0, 16, 16),
+    (4096, 256, 0, 128, 5, 0, 1): (2, 128, 128, "pipelined", "pipelined", 0, 1, 0, 0, 0, 0, 0, 32, 32),
+    (4096, 32, 0, None, 5, 0, 1): (1, 32, 32, "pipelined", "pipelined", 0, 1, 1, 1, 0, 0, 6, 32, 32),
+    (4096, 33, 0, None, 5, 0, 1): (1, 33, 33, "pipelined", "pipelined", 0, 1, 0, 0, 0, 0, 6, 32, 32),
+    (1024, 32, 0, None, 5, 0, 1): (1, 32, 32, "splitk", "splitk", 1, 0, 1, 0, 1, 0, 5, 8, 8),
+    (1024, 33, 0, None, 5, 0, 1): (1, 33, 33, "splitk", "splitk", 1, 0, 0, 0, 0, 0, 5, 8, 8),
+    (16384, 32, 0, None, 5, 0, 1): (1, 32, 32, "pipelined", "pipelined", 0, 1, 1, 1, 0, 0, 6, 128, 128),
+    (16384, 33, 0, None, 5, 0, 1): (1, 33, 33, "pipelined", "pipelined", 0, 1, 0, 0, 0, 0, 6, 128, 128),
+    (256, 1, 0, None, 5, 0, 1): (1, 1, 1, "two_block", "two_block", 0, 1, 0, 0, 0, 0, 0, 2, 2),
+    (256, 16, 0, None, 5, 0, 1): (1, 16, 16, "two_block", "two_block", 0, 1, 0, 0, 0, 0, 0, 2, 2),
+    (256, 384, 0, None, 5, 0, 1): (1, 384, 384, "two_block", "two_block", 0, 1, 0, 0, 0, 0, 0, 2, 2),
+    (256, 385, 0, None, 5, 0, 1): (1, 385, 385, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 2, 2),
+    (224, 2048, 0, None, 5, 0, 1): (1, 2048, 2048, "two_block", "two_block", 0, 1, 0, 0, 0, 0, 0, 2, 2),
+    (225, 2048, 0, None, 5, 0, 1): (1, 2048, 2048, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 2, 2),
+    (200, 1000, 0, None, 5, 0, 1): (1, 1000, 1000, "two_block", "two_block", 0, 1, 0, 0, 0, 0, 0, 2, 2),
+    (128, 1, 0, None, 5, 0, 1): (1, 1, 1, "one_block", "one_block", 0, 1, 0, 0, 0, 0, 0, 1, 1),
+    (129, 1, 0, None, 5, 0, 1): (1, 1, 1, "two_block", "two_block", 0, 1, 0, 0, 0, 0, 0, 2, 2),
+    (128, 4096, 0, None, 5, 0, 1): (1, 4096, 4096, "one_block", "one_block", 0, 1, 0, 0, 0, 0, 0, 1, 1),
+    (256, 16, 0, None, 83, 0, 1): (1, 16, 16, "plain", "plain", 0, 0, 0, 0, 0, 0, 0, 2, 2),
+    (256, 16, 0, None, 84, 0, 1): (1, 16, 16, "plain", "plain", 0, 0, 0, 0, 0, 0, 0, 2, 2),
+    (384, 79, 0, None, 5, 0, 1): (1, 79, 79, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 3, 3),
+    (384, 80, 0, None, 5, 0, 1): (1, 80, 80, "multi_block", "multi_block", 0, 1, 0, 0, 0, 0, 0, 3, 3),
+    (512, 111, 0, None, 5, 0, 1): (1, 111, 111, "splitk", "splitk", 1, 0, 0, 0, 0, 0, 1, 4, 4),
+    (512, 112, 0, None, 5, 0, 1): (1, 112, 112, "multi_block", "multi_block", 1, 0, 0, 0, 0, 0, 0, 4, 4),
+    (640, 143, 0, None, 5, 0, 1): (1, 143, 143, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 5, 5),
+    (640, 144, 0, None, 5, 0, 1): (1, 144, 144, "multi_block", "multi_block", 0, 1, 0, 0, 0, 0, 0, 5, 5),
+    (768, 143, 0, None, 5, 0, 1): (1, 143, 143, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 6, 6),
+    (768, 144, 0, None, 5, 0, 1): (1, 144, 144, "multi_block", "multi_block", 0, 1, 0, 0, 0, 0, 0, 6, 6),
+    (512, 358, 0, None, 5, 0, 1): (1, 358, 358, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 4, 4),
+    (512, 359, 0, None, 5, 0, 1): (1, 359, 359, "multi_block", "multi_block", 0, 1, 0, 0, 0, 0, 0, 4, 4),
+    (384, 358, 0, None, 5, 0, 1): (1, 358, 358, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 3, 3),
+    (384, 359, 0, None, 5, 0, 1): (1, 359, 359, "multi_block", "multi_block", 0, 1, 0, 0, 0, 0, 0, 3, 3),
+    (512, 537, 0, None, 5, 0, 1): (1, 537, 537, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 4, 4),
+    (512, 538, 0, None, 5, 0, 1): (1, 538, 538, "multi_block", "multi_block", 0, 1, 0, 0, 0, 0, 0, 4, 4),
+    (640, 409, 0, None, 5, 0, 1): (1, 409, 409, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 5, 5),
+    (640, 410, 0, None, 5, 0, 1): (1, 410, 410, "multi_block", "multi_block", 0, 1, 0, 0, 0, 0, 0, 5, 5),
+    (768, 409, 0, None, 5, 0, 1): (1, 409, 409, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 6, 6),
+    (768, 410, 0, None, 5, 0, 1): (1, 410, 410, "multi_block", "multi_block", 0, 1, 0, 0, 0, 0, 0, 6, 6),
+    (512, 300, 0, None, 5, 0, 1): (1, 300, 300, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 4, 4),
+    (384, 256, 0, None, 15, 0, 1): (1, 256, 256, "multi_block", "multi_block", 0, 1, 0, 0, 0, 0, 0, 3, 3),
+    (384, 256, 0, None, 16, 0, 1): (1, 256, 256, "multi_block", "multi_block", 0, 1, 0, 0, 0, 0, 0, 3, 3),
+    (512, 256, 0, None, 11, 0, 1): (1, 256, 256, "multi_block", "multi_block", 0, 1, 0, 0, 0, 0, 0, 4, 4),
+    (512, 256, 0, None, 12, 0, 1): (1, 256, 256, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 4, 4),
+    (640, 256, 0, None, 7, 0, 1): (1, 256, 256, "multi_block", "multi_block", 0, 1, 0, 0, 0, 0, 0, 5, 5),
+    (640, 256, 0, None, 8, 0, 1): (1, 256, 256, "multi_block", "multi_block", 0, 1, 0, 0, 0, 0, 0, 5, 5),
+    (768, 256, 0, None, 6, 0, 1): (1, 256, 256, "multi_block", "multi_block", 0, 1, 0, 0, 0, 0, 0, 6, 6),
+    (768, 256, 0, None, 7, 0, 1): (1, 256, 256, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 6, 6),
+    (4096, 256, 0, None, 112, 0, 1): (1, 256, 256, "paired", "paired", 0, 0, 0, 0, 0, 0, 0, 32, 32),
+    (1024, 300, 0, None, 64, 0, 1): (1, 300, 300, "pipelined", "pipelined", 0, 1, 0, 0, 0, 0, 0, 8, 8),
+    (640, 119, 0, None, 5, 0, 1): (1, 119, 119, "splitk_lookahead", "splitk_lookahead", 1, 0, 0, 0, 0, 1, 1, 5, 5),
+    (640, 120, 0, None, 5, 0, 1): (1, 120, 120, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 5, 5),
+    (384, 1, 0, None, 5, 0, 1): (1, 1, 1, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 3, 3),
+    (512, 1, 0, None, 5, 0, 1): (1, 1, 1, "splitk", "splitk", 1, 0, 1, 0, 1, 0, 2, 4, 4),
+    (1024, 46, 0, None, 5, 0, 1): (1, 46, 46, "splitk_lookahead", "splitk_lookahead", 1, 0, 0, 0, 0, 4, 4, 8, 8),
+    (1024, 47, 0, None, 5, 0, 1): (1, 47, 47, "pipelined", "pipelined", 0, 1, 0, 0, 0, 0, 4, 8, 8),
+    (2048, 11, 0, None, 5, 0, 1): (1, 11, 11, "splitk_lookahead", "splitk_lookahead", 1, 0, 1, 1, 1, 8, 13, 16, 16),
+    (2048, 12, 0, None, 5, 0, 1): (1, 12, 12, "pipelined", "pipelined", 0, 1, 1, 1, 0, 0, 12, 16, 16),
+    (4096, 2, 0, None, 5, 0, 1): (1, 2, 2, "splitk_lookahead", "splitk_lookahead", 1, 0, 1, 1, 1, 8, 30, 32, 32),
+    (4096, 3, 0, None, 5, 0, 1): (1, 3, 3, "pipelined", "pipelined", 0, 1, 1, 1, 0, 0, 28, 32, 32),
+    (2048, 4, 0, None, 5, 0, 1): (1, 4, 4, "splitk", "splitk", 1, 0, 1, 0, 1, 0, 14, 16, 16),
+    (2048, 8, 0, None, 5, 0, 1): (1, 8, 8, "splitk", "splitk", 1, 0, 1, 0, 1, 0, 14, 16, 16),
+    (5600, 1, 0, None, 5, 0, 1): (1, 1, 1, "splitk_lookahead", "splitk_lookahead", 1, 0, 1, 1, 1, 8, 42, 44, 44),
+    (6000, 1, 0, None, 5, 0, 1): (1, 1, 1, "splitk_lookahead", "splitk_lookahead", 1, 0, 1, 1, 1, 17, 45, 47, 47),
+    (5000, 1, 0, None, 5, 0, 1): (1, 1, 1, "splitk", "splitk", 1, 0, 1, 0, 1, 0, 38, 40, 40),
+    (3000, 1, 0, None, 5, 0, 1): (1, 1, 1, "splitk", "splitk", 1, 0, 1, 0, 1, 0, 22, 24, 24),
+    (4096, 4, 0, None, 5, 0, 1): (1, 4, 4, "pipelined", "pipelined", 0, 1, 1, 1, 0, 0, 28, 32, 32),
+    (2048, 1, 0, None, 5, 0, 1): (1, 1, 1, "splitk", "splitk", 1, 0, 1, 0, 1, 0, 14, 16, 16),
+    (8192, 1, 0, None, 5, 0, 1): (1, 1, 1, "pipelined", "pipelined", 0, 1, 1, 1, 0, 0, 60, 64, 64),
+    (64, 1, 10, None, 5, 0, 1): (1, 1, 1, "plain", "plain", 0, 0, 0, 0, 0, 0, 0, 1, 2),
+    (256, 256, 100, None, 5, 0, 1): (1, 256, 256, "plain", "plain", 0, 0, 0, 0, 0, 0, 0, 2, 3),
+    (512, 256, 200, None, 5, 0, 1): (1, 256, 256, "plain", "plain", 0, 0, 0, 0, 0, 0, 0, 4, 6),
+    (4096, 256, 1000, None, 5, 0, 1): (1, 256, 256, "paired", "paired", 0, 0, 0, 0, 0, 0, 0, 32, 40),
+    (4096, 1, 1000, None, 5, 0, 1): (1, 1, 1, "splitk", "splitk", 1, 0, 1, 0, 1, 0, 31, 32, 40),
+    (2048, 4, 1000, None, 5, 0, 1): (1, 4, 4, "splitk_lookahead", "splitk_lookahead", 1, 0, 1, 1, 1, 6, 15, 16, 24),
+    (4096, 8, 1000, None, 5, 0, 1): (1, 8, 8, "pipelined", "pipelined", 0, 0, 1, 1, 0, 0, 23, 32, 40),
+    (1024, 1, 1024, None, 5, 0, 1): (1, 1, 1, "splitk", "splitk", 1, 0, 1, 0, 1, 0, 7, 8, 16),
+    (6900, 1, 500, None, 5, 0, 1): (1, 1, 1, "pipelined", "pipelined", 0, 0, 1, 1, 0, 0, 51, 54, 58),
+    (64, 1, 0, None, 5, 1, 1): (1, 1, 1, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 1, 1),
+    (256, 256, 0, None, 5, 1, 1): (1, 256, 256, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 2, 2),
+    (512, 256, 0, None, 5, 1, 1): (1, 256, 256, "plain", "plain", 0, 1, 0, 0, 0, 0, 0, 4, 4),
+    (4096, 1, 0, None, 5, 1, 1): (1, 1, 1, "splitk", "splitk", 1, 0, 1, 0, 1, 0, 30, 32, 32),
+    (4096, 256, 0, None, 5, 1, 1): (1, 256, 256, "paired", "paired", 0, 1, 0, 0, 0, 0, 0, 32, 32),
+    (16384, 1, 0, None, 5, 1, 1): (1, 1, 1, "pipelined", "pipelined", 0, 1, 1, 1, 0, 0, 124, 128, 128),
+    (1024, 1, 0, None, 5, 0, 0): (1, 1, 1, "splitk", "splitk", 1, 0, 0, 0, 1, 0, 6, 8, 8),
+    (4096, 1, 0, None, 5, 0, 0): (1, 1, 1, "splitk", "splitk", 1, 0, 0, 0, 1, 0, 30, 32, 32),
+    (4096, 8, 0, None, 5, 0, 0): (1, 8, 8, "pipelined", "pipelined", 0, 1, 0, 0, 0, 0, 28, 32, 32),
+    (6900, 1, 0, None, 5, 0, 0): (1, 1, 1, "splitk_lookahead", "splitk_lookahead", 1, 0, 0, 0, 1, 32, 52, 54, 54),
+    (16384, 1, 0, None, 5, 0, 0): (1, 1, 1, "pipelined", "pipelined", 0, 1, 0, 0, 0, 0, 124, 128, 128),
+    (4096, 300, 0, 256, 5, 0, 1): (2, 256, 44, "paired", "pipelined", 0, 1, 0, 0, 0, 0, 0, 32, 32),
+    (512, 300, 0, 256, 5, 0, 1): (2, 256, 44, "multi_block", "plain", 0, 1, 0, 0, 0, 0, 0, 4, 4),
+    (64, 300, 0, 256, 5, 0, 1): (2, 256, 44, "one_block", "one_block", 0, 1, 0, 0, 0, 0, 0, 1, 1),
+    (512, 600, 0, 512, 5, 0, 1): (2, 512, 88, "multi_block", "plain", 0, 1, 0, 0, 0, 0, 0, 4, 4),
+    (4096, 40, 0, 16, 5, 0, 1): (3, 16, 8, "pipelined", "pipelined", 0, 1, 1, 1, 0, 0, 14, 32, 32),
+    (1024, 70, 0, 32, 5, 0, 1): (3, 32, 6, "splitk", "splitk", 1, 0, 1, 0, 1, 0, 5, 8, 8),
+    (256, 1000, 0, 384, 5, 0, 1): (3, 384, 232, "two_block", "two_block", 0, 1, 0, 0, 0, 0, 0, 2, 2),
+    (64, 70000, 0, None, 5, 0, 1): (2, 65535, 4465, "one_block", "one_block", 0, 1, 0, 0, 0, 0, 0, 1, 1),
+}
+
+
+def test_plan_query_pins_every_field():
+    """bark_mll_plan_query's complete answer over the thresholds plan_chunk reads (PLAN_TABLE, recorded before the sweep's
+    host code was restructured around it): a refactor of the plan or a moved tuning constant that changes any schedule, step
+    count or hand-over flag fails here.  No GPU needed."""
+    from bark_amd.fitting import schedule_plan
+
+    assert PLAN_FIELDS == tuple(n for n, _ in _lib.MllPlan._fields_)
+    prev = _lib.lib().bark_device_wait(1)
+    try:
+        for (N, B, C, chunk, words, timing, dev_wait), want in PLAN_TABLE.items():
+            _lib.lib().bark_device_wait(dev_wait)
+            d = schedule_plan(N, B, C=C, chunk=chunk, leaf_words=words, timing=bool(timing))
+            assert tuple(d[f] for f in PLAN_FIELDS) == want, ((N, B, C, chunk, words, timing, dev_wait), d)
+    finally:
+        _lib.lib().bark_device_wait(prev)
