@@ -357,6 +357,7 @@ int set_lds_limits() {
         if (e == hipSuccess) e = set(reinterpret_cast<const void *>(solve_narrow_kernel<2>), GEMM_LDS);
         if (e == hipSuccess) e = set(reinterpret_cast<const void *>(solve_narrow_kernel<1, 1>), GEMM_LDS);
         if (e == hipSuccess) e = set(reinterpret_cast<const void *>(solve_narrow_kernel<2, 1>), GEMM_LDS);
+        if (e == hipSuccess) e = set(leaf_inverse_kernel_ptr(), LEAF_INV_LDS_MAX);
         status[dev] = (int)e;
     });
     if (status[dev] != 0)
@@ -1528,6 +1529,10 @@ int bark_kernel_inverse_leafspace_hip(bark_ctx *ctx, const void *packed, const b
     if (!kinv_out) {
         error_buffer()[0] = 0;
         return fail(BARK_ERR_ARG, "bark_kernel_inverse_leafspace_hip: kinv_out is null");
+    }
+    if (info && info->m > LEAF_INV_MAX_TREES) {  // before any launch: leaf_inverse_kernel's leaf lists must fit its LDS
+        error_buffer()[0] = 0;
+        return fail(BARK_ERR_ARG, "leaf-space inverse supports at most %d trees (got %lld)", LEAF_INV_MAX_TREES, (long long)info->m);
     }
     return leafspace_run(ctx, packed, info, X, N, d, y, noise, scale, flags, nullptr, 0, mll_out, nullptr, nullptr, kinv_out,
                          kinv_y_out, info_out, workspace, workspace_bytes, Bc, stream_);

@@ -61,6 +61,12 @@ int ctx_events(bark_ctx *ctx, size_t n);          // at least n events in ctx->e
 int ctx_chain_streams(bark_ctx *ctx, size_t n);   // at least n chain streams + events
 int set_lds_limits();                             // once per device: kernels with > 64 KiB of dynamic LDS (chol.hip)
 
+// leaf-space inverse (leafspace.hip): leaf_inverse_kernel keeps the leaf lists of its 64 columns in dynamic LDS, m x 64
+// 16-bit ids, so it takes forests of at most 160 KiB / 128 B = 1280 trees
+constexpr int LEAF_INV_MAX_TREES = 1280;
+constexpr size_t LEAF_INV_LDS_MAX = (size_t)LEAF_INV_MAX_TREES * 64 * sizeof(unsigned short);
+const void *leaf_inverse_kernel_ptr();            // for set_lds_limits
+
 constexpr size_t STAGE_BYTES = 64 * 1024;  // bark_ctx::stage_host / stage_dev
 constexpr int NODE_BYTES = 26;          // forest.py:8-19, packed
 constexpr uint32_t LEAF_FLAG = 0x80000000u;

@@ -253,6 +253,8 @@ __global__ __launch_bounds__(256) void leaf_inverse_kernel(const uint32_t *__res
 
 }  // namespace
 
+const void *leaf_inverse_kernel_ptr() { return reinterpret_cast<const void *>(leaf_inverse_kernel); }
+
 int leafspace_predict(const uint32_t *ccodes, int W, int cpad, int C, const double *w, const double *Minv, int R,
                       const double *noise, const double *scale, int m, int bc, double *mu, double *var, hipStream_t s) {
     if (m > LP_MAX_TREES) return fail(BARK_ERR_ARG, "leaf-space posterior supports at most %d trees", LP_MAX_TREES);
@@ -265,7 +267,8 @@ int leafspace_predict(const uint32_t *ccodes, int W, int cpad, int C, const doub
 int leafspace_inverse(const uint32_t *codes, int W, int npad, int N, const double *Minv, const double *w, int R,
                       const double *y, const double *noise, const double *scale, int m, int bc, double *Wm, double *kinv,
                       double *kinv_y, hipStream_t s) {
-    if (R > 65535 || m > 16384) return fail(BARK_ERR_ARG, "leaf-space inverse: forest too large (R = %d, m = %d)", R, m);
+    if (R > 65535 || m > LEAF_INV_MAX_TREES)
+        return fail(BARK_ERR_ARG, "leaf-space inverse supports at most %d trees (got m = %d, R = %d)", LEAF_INV_MAX_TREES, m, R);
     hipLaunchKernelGGL(leaf_rowsum_kernel, dim3((unsigned)((N + 3) / 4), (unsigned)bc), dim3(256), 0, s, codes, W, npad, N, Minv,
                        w, R, y, noise, scale, m, Wm, kinv_y);
     BARK_LAUNCH_CHECK();

@@ -300,7 +300,9 @@ int bark_mll_leafspace_hip(bark_ctx *ctx, const void *packed, const bark_pack_in
  * (opt_model.py:54-59) — without factorising the N x N matrix:
  *   K_s^-1 = (I - c Z M^-1 Z') / s2 ,   K_s^-1 y = (y - c Z w) / s2 ,   log|K_s| = -2 mll - y'K_s^-1 y
  * (mll in the convention selected by `flags`, as above).  kinv_out: (B, N, N); kinv_y_out: (B, N) or NULL.
- * Cost: the R x R sweep with an identity right-hand side + N R m + N^2 m gathered adds. */
+ * Cost: the R x R sweep with an identity right-hand side + N R m + N^2 m gathered adds.
+ * Limits: m <= 1280 trees (the leaf lists of a 64-column output tile, m x 64 16-bit ids, sit in the 160 KiB of LDS) and
+ * R <= 8192 leaves, else BARK_ERR_ARG before anything is launched. */
 size_t bark_kernel_inverse_leafspace_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t Bc);
 int bark_kernel_inverse_leafspace_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N,
                                       int64_t d, const double *y, const double *noise, const double *scale, int flags,

@@ -12,8 +12,7 @@ from bark_amd import _lib, forest as bf, synthetic
 from oracle import oracle as orc
 
 from conftest import ROOT, load_golden
-
-LEAF, CAT, FEAT = 0x80000000, 0x40000000, 0x3FFFFFFF
+from leafspace_ref import host_pack, walk_packed
 
 
 def test_library_exports_every_declared_symbol():
@@ -29,35 +28,6 @@ def test_library_exports_every_declared_symbol():
     assert lib.bark_version() == 210
     assert lib.bark_last_error() == b""
     assert lib.bark_leaf_npad(1) == 128 and lib.bark_leaf_npad(128) == 128 and lib.bark_leaf_npad(129) == 256
-
-
-def host_pack(nodes3, ft):
-    lib = _lib.lib()
-    info = _lib.PackInfo()
-    B, m, L = nodes3.shape
-    nodes3 = np.ascontiguousarray(nodes3)
-    ft = np.ascontiguousarray(ft, dtype=np.int64)
-    _lib.check(lib.bark_forest_pack_info(_lib.ptr(nodes3), B, m, L, _lib.ptr(ft), ft.shape[0], ctypes.byref(info)))
-    packed = np.zeros(info.packed_bytes // 4, dtype=np.uint32)
-    _lib.check(lib.bark_forest_pack(_lib.ptr(nodes3), _lib.ptr(ft), ft.shape[0], ctypes.byref(info), _lib.ptr(packed)))
-    return info, packed.reshape(B, m, info.stride, 4)
-
-
-def walk_packed(packed_tree, x, max_depth):
-    """numpy emulation of the device walk (traverse.hip) on the wire format."""
-    n = packed_tree[0]
-    for _ in range(max_depth):
-        if n[0] & LEAF:
-            break
-        f = int(n[0] & FEAT)
-        if n[0] & CAT:
-            xt = np.trunc(x[f])
-            left = bool((int(n[1]) >> int(xt)) & 1) if 0 <= xt < 32 else False
-        else:
-            left = x[f] <= float(np.uint32(n[1]).view(np.float32))
-        n = packed_tree[int(n[2] if left else n[3])]
-    assert n[0] & LEAF
-    return int(n[1]), int(n[0] & 0xFF), int(n[2])
 
 
 @pytest.mark.parametrize("name", ["g1_kat_tree", "g3_prior_mixed_n64", "g5_boundaries", "g7_tree_function"])
