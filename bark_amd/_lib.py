@@ -50,6 +50,14 @@ class MllPlan(ctypes.Structure):
         "pre_update", "lookahead_steps", "splitk_steps", "nrb", "ncb")]
 
 
+class FrontendVariant(ctypes.Structure):
+    """bark_frontend_variant (include/bark_hip_testing.h): which leaf-walk and Gram kernels a shape takes."""
+    _fields_ = [(n, ctypes.c_int32) for n in (
+        "encoding", "words", "codes_grouped", "codes_nodes_lds", "codes_x_lds", "codes_workgroups", "indices_staged",
+        "gram_rep", "gram_tile_rows", "gram_tile_cols", "gram_vec2")]
+
+
+GRAM_REPS = ("bytes8", "bytes7", "bits")  # bark_frontend_variant.gram_rep
 SCHEDULES = ("one_block", "plain", "paired", "pipelined", "splitk", "splitk_lookahead", "two_block", "multi_block")  # BARK_SCHED_*
 
 
@@ -61,6 +69,7 @@ SIGNATURES = {
     "bark_xcd_map_selftest": (ci, [ci, ci]),
     "bark_mll_plan_query": (ci, [i64, i64, i64, i64, i64, ci, ci, ctypes.POINTER(MllPlan)]),
     "bark_debug_fail_launch": (ctypes.c_long, [ctypes.c_long]),
+    "bark_frontend_variant_query": (ci, [ctypes.POINTER(PackInfo), i64, i64, i64, i64, i64, ci, ctypes.POINTER(FrontendVariant)]),
     "bark_dev_alloc": (ci, [vp, ctypes.c_size_t, ctypes.POINTER(vp)]),
     "bark_dev_free": (ci, [vp, vp]),
     "bark_ctx_upload": (ci, [vp, vp, vp, ctypes.c_size_t, vp]),

@@ -98,6 +98,23 @@ inline LeafRep leaf_rep(const bark_pack_info *info) {
     if (bark_leaf_encoding(info) == BARK_LEAF_BITS) return REP_BITS;
     return info->max_leaves <= 128 ? REP_BYTES7 : REP_BYTES8;
 }
+// Launch decisions of the front end as pure host functions of the shape (traverse.hip, gram.hip): the launchers launch what these
+// return and bark_frontend_variant_query (include/bark_hip_testing.h) reports it.
+struct WalkVariant {
+    bool grouped;       // leaf_walk_grouped_kernel (codes only), else leaf_walk_kernel
+    bool nodes_lds;     // grouped: the forest's packed nodes are walked in LDS
+    bool x_lds;         // the point rows sit in LDS (always when grouped); MODE 0: and the results are staged there
+    unsigned grid_x;    // workgroups per forest of the kernel taken
+    int64_t plain_wgs;  // grid of the one-thread-per-point kernel, which the grouped rule looks at
+    size_t lds;         // dynamic LDS of the launch
+};
+WalkVariant walk_variant(int mode, const bark_pack_info *info, int64_t N, int64_t d, int words);
+struct GramVariant {
+    int tile_rows, tile_cols;  // output tile of a workgroup
+    bool vec2;                 // every output row starts on a 16-byte boundary
+    size_t lds;                // dynamic LDS of the launch: the two code strips
+};
+GramVariant gram_variant(int words, int64_t ld, int64_t batch_stride, uintptr_t out_address);
 // per code word: number of disagreeing trees (byte encodings) or of agreeing trees (one-hot bits)
 template <int REP>
 __device__ __forceinline__ uint32_t code_count(uint32_t a, uint32_t b) {

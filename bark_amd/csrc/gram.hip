@@ -153,6 +153,21 @@ __global__ __launch_bounds__(GRAM_THREADS) void gram_kernel(GramArgs p) {
 
 }  // namespace
 
+// Which instantiation a Gram fill takes, from the code width and the output's layout alone.  Pure host code: launch_gram launches
+// what this returns and bark_frontend_variant_query reports it.  The wide tile while its two strips of `words` planes fit 64 KiB
+// of LDS (GRAM_TC_WIDE = 128: up to 102 words), else the narrow one; 16-byte stores throughout (VEC2) when every row of every
+// matrix starts on a 16-byte boundary.
+GramVariant gram_variant(int words, int64_t ld, int64_t batch_stride, uintptr_t out_address) {
+    auto tile_rows = [](int tc) { return 8 * (GRAM_THREADS / (tc / 2)); };
+    auto strips = [&](int tc) { return (size_t)words * (tile_rows(tc) + tc) * sizeof(uint32_t); };
+    GramVariant v{};
+    v.tile_cols = strips(GRAM_TC_WIDE) <= 64 * 1024 ? GRAM_TC_WIDE : GRAM_TC_NARROW;
+    v.tile_rows = tile_rows(v.tile_cols);
+    v.lds = strips(v.tile_cols);
+    v.vec2 = (ld % 2 == 0) && (batch_stride % 2 == 0) && ((out_address & 15) == 0);
+    return v;
+}
+
 // shared with chol.hip (the MLL engine fills its workspace with this kernel)
 int launch_gram(const uint32_t *leaf1, int npad1, const uint32_t *leaf2, int npad2, int64_t B, int64_t m, int N, int M,
                 int Nout, int Mout, const double *shift, const double *scale, const double *noise, double *out, int64_t ld,
@@ -177,11 +192,12 @@ int launch_gram(const uint32_t *leaf1, int npad1, const uint32_t *leaf2, int npa
     p.pad_identity = pad_identity;
     p.upper_only = upper_only;
     if (B > 65535) return fail(BARK_ERR_ARG, "gram: at most 65535 forests per call");
-    const bool vec2 = (ld % 2 == 0) && (batch_stride % 2 == 0) && ((reinterpret_cast<uintptr_t>(out) & 15) == 0);
+    const GramVariant v = gram_variant(words, ld, batch_stride, reinterpret_cast<uintptr_t>(out));
+    const bool vec2 = v.vec2;
     auto launch = [&](auto tc_tag) -> int {
         constexpr int TC = decltype(tc_tag)::value, TR = 8 * (GRAM_THREADS / (TC / 2));
         dim3 grid((unsigned)((Mout + TC - 1) / TC), (unsigned)((Nout + TR - 1) / TR), (unsigned)B);
-        const size_t lds = (size_t)p.W * (TR + TC) * sizeof(uint32_t);
+        const size_t lds = v.lds;
         if (lds > 64 * 1024) return fail(BARK_ERR_ARG, "gram: too many trees (m=%lld)", (long long)m);
 #define BARK_GRAM_LAUNCH(R)                                                                                   \
     do {                                                                                                      \
@@ -199,9 +215,7 @@ int launch_gram(const uint32_t *leaf1, int npad1, const uint32_t *leaf2, int npa
 #undef BARK_GRAM_LAUNCH
         return BARK_OK;
     };
-    constexpr int WIDE_TR = 8 * (GRAM_THREADS / (GRAM_TC_WIDE / 2));
-    const bool wide = (size_t)p.W * (WIDE_TR + GRAM_TC_WIDE) * sizeof(uint32_t) <= 64 * 1024;
-    const int rc = wide ? launch(std::integral_constant<int, GRAM_TC_WIDE>{}) : launch(std::integral_constant<int, GRAM_TC_NARROW>{});
+    const int rc = v.tile_cols == GRAM_TC_WIDE ? launch(std::integral_constant<int, GRAM_TC_WIDE>{}) : launch(std::integral_constant<int, GRAM_TC_NARROW>{});
     if (rc) return rc;
     BARK_LAUNCH_CHECK();
     return BARK_OK;
@@ -224,4 +238,29 @@ extern "C" int bark_gram_from_leaves_hip(const uint32_t *leaf1, int64_t N, const
     return launch_gram(leaf1, (int)bark_leaf_npad(N), leaf2, (int)bark_leaf_npad(M), B, m, (int)N, (int)M, (int)N,
                        (int)M, shift, scale, noise, out, ld, batch_stride, false, false, (int)leaf_rep(info),
                        (int)bark_leaf_words(info), static_cast<hipStream_t>(stream));
+}
+
+// include/bark_hip_testing.h
+extern "C" int bark_frontend_variant_query(const bark_pack_info *info, int64_t N, int64_t M, int64_t d, int64_t ld,
+                                           int64_t batch_stride, int out_mod16, bark_frontend_variant *out) {
+    error_buffer()[0] = 0;
+    if (!info || !out || N < 1 || M < 1 || d < 1 || info->B < 1 || info->m < 1 || info->stride < 1 || out_mod16 < 0 || out_mod16 > 15)
+        return fail(BARK_ERR_ARG, "bark_frontend_variant_query: bad argument");
+    const int words = (int)bark_leaf_words(info);
+    const bool bits = bark_leaf_encoding(info) == BARK_LEAF_BITS;
+    const WalkVariant c1 = walk_variant(bits ? 2 : 1, info, N, d, words);
+    const WalkVariant ix = walk_variant(0, info, N, d, words);
+    const GramVariant g = gram_variant(words, ld, batch_stride, (uintptr_t)out_mod16);
+    out->encoding = bits ? BARK_LEAF_BITS : BARK_LEAF_BYTES;
+    out->words = words;
+    out->codes_grouped = c1.grouped;
+    out->codes_nodes_lds = c1.nodes_lds;
+    out->codes_x_lds = c1.x_lds;
+    out->codes_workgroups = (int32_t)(c1.plain_wgs > INT32_MAX ? INT32_MAX : c1.plain_wgs);
+    out->indices_staged = ix.x_lds;
+    out->gram_rep = (int32_t)leaf_rep(info);
+    out->gram_tile_rows = g.tile_rows;
+    out->gram_tile_cols = g.tile_cols;
+    out->gram_vec2 = g.vec2;
+    return BARK_OK;
 }

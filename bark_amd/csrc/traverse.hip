@@ -219,41 +219,63 @@ int launch_walk(const void *packed, const bark_pack_info *info, const double *X,
     if (MODE != 0 && !force_words && words > MAX_LEAF_WORDS)
         return fail(BARK_ERR_ARG, "forest needs %d leaf-code words per point (max %d): too many leaves in total", words,
                     MAX_LEAF_WORDS);
-    const int64_t extent = MODE != 0 ? npad : N;
-    dim3 grid((unsigned)((extent + WALK_THREADS - 1) / WALK_THREADS), (unsigned)info->B);
-    const size_t lds = (size_t)WALK_THREADS * (d | 1) * sizeof(double) +
-                       (MODE == 0 ? (size_t)WALK_THREADS * (IDX_CHUNK + 1) * sizeof(uint32_t) : 0);  // + MODE 0's staging tile
+    const WalkVariant v = walk_variant(MODE, info, N, d, words);
+    const dim3 grid(v.grid_x, (unsigned)info->B);
     hipStream_t s = static_cast<hipStream_t>(stream);
     const uint4 *nodes = static_cast<const uint4 *>(packed);
+#define BARK_WALK_LAUNCH(...)                                                                                          \
+    hipLaunchKernelGGL((__VA_ARGS__), grid, dim3(WALK_THREADS), v.lds, s, nodes, (int)info->stride, (int)info->m,           \
+                       (int)info->max_depth, X, (int)N, (int)d, (int)npad, words, out, fault)
     if constexpr (MODE != 0) {
-        // X rows (32 x (d | 1) doubles: a multiple of 16 bytes as 32 doubles are), the accumulator words rounded up to 16 bytes, the nodes
-        const size_t gacc = MODE == 2 ? (((size_t)WALK_POINTS * words + 3) & ~(size_t)3) * sizeof(uint32_t) : 0;
-        const size_t glds = (size_t)WALK_POINTS * (d | 1) * sizeof(double) + gacc;
-        const size_t gnodes = (size_t)info->m * info->stride * sizeof(uint4);
-        if ((int64_t)grid.x * grid.y < WALK_GROUPED_MAX_WGS && glds <= 64 * 1024) {  // too few workgroups to hide the chains: share a point's trees out
-            const dim3 gg((unsigned)((npad + WALK_POINTS - 1) / WALK_POINTS), (unsigned)info->B);
-            if (BARK_WALK_NODES_LDS && glds + gnodes <= 32 * 1024)
-                hipLaunchKernelGGL((leaf_walk_grouped_kernel<MODE, true>), gg, dim3(WALK_THREADS), glds + gnodes, s, nodes, (int)info->stride,
-                                   (int)info->m, (int)info->max_depth, X, (int)N, (int)d, (int)npad, words, out, fault);
+        if (v.grouped) {  // too few workgroups to hide the chains: share a point's trees out
+            if (v.nodes_lds)
+                BARK_WALK_LAUNCH(leaf_walk_grouped_kernel<MODE, true>);
             else
-                hipLaunchKernelGGL((leaf_walk_grouped_kernel<MODE, false>), gg, dim3(WALK_THREADS), glds, s, nodes, (int)info->stride,
-                                   (int)info->m, (int)info->max_depth, X, (int)N, (int)d, (int)npad, words, out, fault);
+                BARK_WALK_LAUNCH(leaf_walk_grouped_kernel<MODE, false>);
             BARK_LAUNCH_CHECK();
             return BARK_OK;
         }
     }
-    if (lds <= 64 * 1024) {
-        hipLaunchKernelGGL((leaf_walk_kernel<MODE, true>), grid, dim3(WALK_THREADS), lds, s, nodes, (int)info->stride,
-                           (int)info->m, (int)info->max_depth, X, (int)N, (int)d, (int)npad, words, out, fault);
-    } else {
-        hipLaunchKernelGGL((leaf_walk_kernel<MODE, false>), grid, dim3(WALK_THREADS), 0, s, nodes, (int)info->stride,
-                           (int)info->m, (int)info->max_depth, X, (int)N, (int)d, (int)npad, words, out, fault);
-    }
+    if (v.x_lds)
+        BARK_WALK_LAUNCH(leaf_walk_kernel<MODE, true>);
+    else
+        BARK_WALK_LAUNCH(leaf_walk_kernel<MODE, false>);
+#undef BARK_WALK_LAUNCH
     BARK_LAUNCH_CHECK();
     return BARK_OK;
 }
 
 }  // namespace
+
+// Which kernel a walk of N points takes, its grid and its dynamic LDS, from the shape alone.  Pure host code: launch_walk launches
+// exactly what this returns and bark_frontend_variant_query (gram.hip) reports it, so every threshold below exists once.
+//   MODE 1 / 2 (codes): grids of the one-thread-per-point kernel below WALK_GROUPED_MAX_WGS workgroups take the grouped kernel while
+//   32 point rows (+ MODE 2's accumulator words) fit 64 KiB, with the forest's nodes in LDS while everything fits 32 KiB;
+//   every mode: the plain kernel keeps 256 point rows (+ MODE 0's staging tile) in LDS while they fit 64 KiB, else reads X from
+//   global memory (and MODE 0 stores directly).
+WalkVariant walk_variant(int mode, const bark_pack_info *info, int64_t N, int64_t d, int words) {
+    WalkVariant v{};
+    const int64_t npad = bark_leaf_npad(N), extent = mode != 0 ? npad : N;
+    v.grid_x = (unsigned)((extent + WALK_THREADS - 1) / WALK_THREADS);
+    v.plain_wgs = (int64_t)v.grid_x * info->B;
+    const size_t lds = (size_t)WALK_THREADS * (d | 1) * sizeof(double) +
+                       (mode == 0 ? (size_t)WALK_THREADS * (IDX_CHUNK + 1) * sizeof(uint32_t) : 0);  // + MODE 0's staging tile
+    v.x_lds = lds <= 64 * 1024;
+    v.lds = v.x_lds ? lds : 0;
+    if (mode != 0) {
+        // X rows (32 x (d | 1) doubles: a multiple of 16 bytes as 32 doubles are), the accumulator words rounded up to 16 bytes, the nodes
+        const size_t gacc = mode == 2 ? (((size_t)WALK_POINTS * words + 3) & ~(size_t)3) * sizeof(uint32_t) : 0;
+        const size_t glds = (size_t)WALK_POINTS * (d | 1) * sizeof(double) + gacc;
+        const size_t gnodes = (size_t)info->m * info->stride * sizeof(uint4);
+        if (v.plain_wgs < WALK_GROUPED_MAX_WGS && glds <= 64 * 1024) {
+            v.grouped = v.x_lds = true;
+            v.nodes_lds = BARK_WALK_NODES_LDS && glds + gnodes <= 32 * 1024;
+            v.grid_x = (unsigned)((npad + WALK_POINTS - 1) / WALK_POINTS);
+            v.lds = glds + (v.nodes_lds ? gnodes : 0);
+        }
+    }
+    return v;
+}
 
 // one-hot leaf code with `words` = ceil(max_bits / 32) planes, whatever encoding the Gram kernels would pick
 int walk_one_hot(const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d, int words,

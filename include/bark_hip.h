@@ -165,7 +165,9 @@ int bark_leaf_indices_hip(bark_ctx *ctx, const void *packed, const bark_pack_inf
  *                   bit of the leaf it reaches in every tree; then  #agreeing trees = popcount(z_i & z_j)
  *                   (2 VALU per 32 bits).  Chosen when max_bits < 64 * ceil(m/4), and always for trees with
  *                   more than 256 leaves.
- *   BARK_LEAF_BYTES 4 dense 8-bit leaf ids per dword; a tree pair agrees iff its byte of z_i ^ z_j is zero. */
+ *   BARK_LEAF_BYTES 4 dense 8-bit leaf ids per dword; a tree pair agrees iff its byte of z_i ^ z_j is zero.
+ * Every plane entry N <= i < Npad is written as ZERO, in both encodings and by every walk kernel: all B * W * Npad words are
+ * defined after the call and nothing behind them is touched.  At most 112 words per point (else BARK_ERR_ARG). */
 enum { BARK_LEAF_BYTES = 0, BARK_LEAF_BITS = 1 };
 int64_t bark_leaf_npad(int64_t N);
 int bark_leaf_encoding(const bark_pack_info *info);

@@ -318,7 +318,11 @@ def test_fuzz_scrambled_containers_and_boundary_points(B):
 
 
 def test_wide_feature_matrix_walks_from_global_memory(B):
-    """d = 40 > 31: the point rows no longer fit the walk kernel's LDS tile (leaf_walk_kernel<., false>)."""
+    """d = 40: for the INDEX walk (pass_through_forest, MODE 0) 256 point rows plus the staging tile no longer fit the LDS, so it
+    reads X from global memory and stores directly (leaf_walk_kernel<0, false>, from d = 16).  The CODE walk of the Gram calls does
+    not: at B = 2 its grid is far below the grouped threshold and 32 rows of d = 40 fit, so it is leaf_walk_grouped_kernel with X
+    in LDS.  The plain code kernels with X in global memory (d >= 32 on a grid of >= 2048 workgroups, or d > 255) are covered by
+    tests/test_gpu_frontend.py."""
     rng = np.random.default_rng(40)
     d, N = 40, 333
     X = rng.uniform(size=(N, d))
