@@ -466,7 +466,7 @@ __global__ __launch_bounds__(LR_THREADS) void small_kernel(const double *__restr
                 acc = -1;
             } else {
                 const double log_alpha = dec.log_q_prior[b] + 0.5 * (q - logsum);
-                acc = (dec.log_u[b] <= fmin(log_alpha, 0.0)) ? 1 : 0;  // NaN compares false: reject
+                acc = (dec.log_u[b] <= log_alpha && dec.log_u[b] <= 0.0) ? 1 : 0;  // a NaN on either side compares false: reject
             }
             dec.accept_out[b] = acc;
             if (acc > 0) {
@@ -677,6 +677,8 @@ void launch_rewrite(hipStream_t stream, const double *K, int N, int r, const dou
 // Metropolis decision of one tree proposal per chain on the device (bark_sampler.py:256-264):
 //   log_alpha = log_q_prior + (new_mll - cur_mll),  new_mll - cur_mll = 0.5 (dquad - dlogdet)   (scalars = {dquad, dlogdet})
 //   accept iff log(u) <= min(log_alpha, 0);  on accept the chain's running y'K^-1 y and log|K| move with it.
+//   (Python's min: a NaN log_alpha gives NaN and rejects.  fmin(NaN, 0) is 0 and would accept every such proposal, so the
+//   rule is written as two comparisons.)
 // accept_out: 1 / 0, or -1 when the r x r system was singular (the reference raises LinAlgError there).  A chain that
 // met a singular system stays at -1 for the rest of the sweep (accept_prev = the previous step's flags, null for the
 // first): its K_inv is not rewritten again, so K_inv, quad and logdet of that chain still belong together — the state
@@ -693,7 +695,7 @@ __global__ void decide_kernel(const double *__restrict__ scalars, const double *
         acc = -1;
     } else {
         const double log_alpha = log_q_prior[b] + 0.5 * (dquad - dlogdet);
-        acc = (log_u[b] <= fmin(log_alpha, 0.0)) ? 1 : 0;  // NaN compares false: reject
+        acc = (log_u[b] <= log_alpha && log_u[b] <= 0.0) ? 1 : 0;  // a NaN on either side compares false: reject
     }
     accept_out[b] = acc;
     if (acc > 0) {
