@@ -97,6 +97,9 @@ SIGNATURES = {
     "bark_copy2d_hip": (ci, [vp, i64, vp, i64, i64, i64, vp]),
     "bark_tree_sweep_chains_hip": (ci, [vp, vp, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp,
                                         ctypes.c_size_t, vp]),
+    "bark_noise_scale_step_chains_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64]),
+    "bark_noise_scale_step_chains_hip": (ci, [vp, vp, i64, i64, vp, ctypes.POINTER(PackInfo), vp, i64, vp, vp, vp, vp, vp, vp,
+                                              vp, vp, ctypes.c_size_t, vp]),
     "bark_lowrank_status_hip": (ci, [vp, i64, i64, ctypes.POINTER(ctypes.c_int32), vp]),
     "bark_leaf_npad": (i64, [i64]),
     "bark_leaf_encoding": (ci, [ctypes.POINTER(PackInfo)]),

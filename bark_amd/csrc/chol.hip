@@ -71,7 +71,12 @@ int leafspace_predict(const uint32_t *ccodes, int W, int cpad, int C, const doub
                       const double *noise, const double *scale, int m, int bc, double *mu, double *var, hipStream_t s);
 int leafspace_inverse(const uint32_t *codes, int W, int npad, int N, const double *Minv, const double *w, int R,
                       const double *y, const double *noise, const double *scale, int m, int bc, double *Wm, double *kinv,
-                      double *kinv_y, hipStream_t s);
+                      double *kinv_y, const int32_t *accept, hipStream_t s);
+int noise_scale_decide(const double *new_mll, const double *state, const double *noise, const double *log_q_prior,
+                       const double *log_u, const int32_t *info, const int32_t *fault, int nc, int32_t *accept_out,
+                       hipStream_t s);
+int noise_scale_state(const double *kinv_y, const double *y, int N, const double *new_mll, const int32_t *accept, int nc,
+                      double *state, hipStream_t s);
 int leafspace_finish(const double *accum, const double *yy, const double *noise, const double *scale, int m, int bc, int N,
                      int include_2pi, double *mll, hipStream_t s);
 int64_t sample_spad(int64_t S);
@@ -1384,6 +1389,16 @@ size_t bark_posterior_samples_workspace_bytes(int64_t N, int64_t max_bits, int64
     return make_leaf_layout(N, max_bits, m, Bc, C, false, S).total;
 }
 
+// noise/scale step: the leaf-space inverse layout of one chunk of nc forests, then new_mll (nc), the sweep's info (nc) and
+// K^-1 y (nc, N)
+size_t bark_noise_scale_step_chains_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t nc) {
+    if (N < 1 || max_bits < 1 || m < 1 || nc < 1) return 0;
+    size_t o = make_leaf_layout(N, max_bits, m, nc, 0, true).total;
+    o = align256(o + (size_t)nc * sizeof(double));
+    o = align256(o + (size_t)nc * sizeof(int32_t));
+    return align256(o + (size_t)nc * N * sizeof(double));
+}
+
 }  // extern "C"
 
 // Joint draws at the candidates (bark_posterior_samples_hip): S > 0, eps (B, S, R), and f_out (B, S, C) for
@@ -1395,6 +1410,44 @@ struct LeafDraws {
     double *f_out = nullptr, *red_out = nullptr;
     int64_t *idx_out = nullptr;
 };
+
+// One chunk of the leaf-space system, shared by leafspace_run and the noise/scale step (sub->B forests): leaf walk, I + c Z'Z and
+// v = Z'y, the identity right-hand side when M^-1 is wanted (the sweep then also yields V = U^-T), the R x R sweep and, with
+// `mll`, the MLL.  `info` receives the sweep's pivot status.
+static int leafspace_factor_chunk(bark_ctx *ctx, Sweep &sw, const SweepShape &sh, const LeafLayout &g, const void *packed_c,
+                                  const bark_pack_info *sub, const double *X, int64_t N, int64_t d, const double *y,
+                                  const double *yy, const double *noise, const double *scale, bool want_minv, int include_2pi,
+                                  int32_t *info, double *mll, uint32_t *codes, unsigned long long *planes, hipStream_t caller) {
+    const int bc = (int)sub->B, m = (int)sub->m;
+    Mats &p = sw.p;
+    int rc;
+    sw.configure(plan_chunk(sh, bc, false, false, sw.panel != sw.main, SweepPath::LeafSpace), bc);
+    p.info = info;
+    if ((rc = walk_one_hot(packed_c, sub, X, N, d, (int)g.W, codes, ctx->fault, caller))) return rc;
+    rc = leafspace_prepare(codes, (int)g.W, (int)g.npad, planes, (int)g.R, (int)g.Rpad, noise, scale, m, bc, p.A, p.ld, p.bstride, y,
+                           (int)N, p.yz, p.accum, p.info, caller);
+    if (rc) return rc;
+    if (want_minv) {
+        dim3 gi((unsigned)((g.L.cpad + 255) / 256), (unsigned)g.L.npad, (unsigned)bc);
+        hipLaunchKernelGGL(identity_rhs_kernel, gi, dim3(256), 0, caller, p, (int)g.R, (int)g.L.cpad);
+        BARK_LAUNCH_CHECK();
+    }
+    if ((rc = sw.factor())) return rc;
+    if (mll) return leafspace_finish(p.accum, yy, noise, scale, m, bc, (int)N, include_2pi, mll, caller);
+    return BARK_OK;
+}
+
+// w = M^-1 v = V'z and M^-1 = V'V from the swept chunk (the same kernels the dense posterior / inverse export use)
+static int leafspace_minv(Sweep &sw, const LeafLayout &g, int bc, double *wvec, double *Minv, hipStream_t caller) {
+    const int R = (int)g.R;
+    int rc = launch_predict_reduce(sw.p, R, R, bc, nullptr, wvec, nullptr, g.L.splitk ? sw.slabs : nullptr, caller);
+    if (rc) return rc;
+    const int nct = (int)(g.L.cpad / NB);
+    hipLaunchKernelGGL(vtv_kernel, dim3(xcd_grid(nct * nct, bc)), dim3(THREADS), GEMM_LDS, caller, sw.p, nct, R,
+                       (const double *)nullptr, 1.0, 1, Minv);
+    BARK_LAUNCH_CHECK();
+    return BARK_OK;
+}
 
 // shared driver of the leaf-space entry points: MLL (unless mll_out is null and draws are asked for); posterior when C > 0;
 // explicit inverse when kinv_out; joint draws at the candidates when draws.S > 0
@@ -1447,24 +1500,10 @@ static int leafspace_run(bark_ctx *ctx, const void *packed, const bark_pack_info
         bark_pack_info sub = *info;
         sub.B = bc;
         const char *packed_c = static_cast<const char *>(packed) + (size_t)c0 * m * info->stride * 16;
-        sw.configure(plan_chunk(sh, bc, false, false, sw.panel != sw.main, SweepPath::LeafSpace), bc);
-        p.info = info_out + c0;
-        if ((rc = walk_one_hot(packed_c, &sub, X, N, d, (int)g.W, codes, ctx->fault, caller))) return rc;
-        rc = leafspace_prepare(codes, (int)g.W, (int)g.npad, planes, (int)g.R, (int)g.Rpad, noise + c0,
-                               use_scale ? scale + c0 : nullptr, (int)m, (int)bc, p.A, p.ld, p.bstride, y, (int)N, p.yz,
-                               p.accum, p.info, caller);
+        rc = leafspace_factor_chunk(ctx, sw, sh, g, packed_c, &sub, X, N, d, y, yy, noise + c0, use_scale ? scale + c0 : nullptr,
+                                    want_minv, (flags & BARK_MLL_INCLUDE_2PI) ? 1 : 0, info_out + c0, mll_out ? mll_out + c0 : nullptr,
+                                    codes, planes, caller);
         if (rc) return rc;
-        if (want_minv) {  // right-hand side block := I_R, so the sweep also yields V = U^-T
-            dim3 gi((unsigned)((g.L.cpad + 255) / 256), (unsigned)g.L.npad, (unsigned)bc);
-            hipLaunchKernelGGL(identity_rhs_kernel, gi, dim3(256), 0, caller, p, (int)g.R, (int)g.L.cpad);
-            BARK_LAUNCH_CHECK();
-        }
-        if ((rc = sw.factor())) return rc;
-        if (mll_out) {
-            rc = leafspace_finish(p.accum, yy, noise + c0, use_scale ? scale + c0 : nullptr, (int)m, (int)bc, (int)N,
-                                  (flags & BARK_MLL_INCLUDE_2PI) ? 1 : 0, mll_out + c0, caller);
-            if (rc) return rc;
-        }
         if (want_minv && sampling) {
             // w = M^-1 v = V'z; then Wt = c w 1' + sqrt(scale/m) V' E' and the gather over the candidates' leaves (sample.hip)
             const int R = (int)g.R, S = (int)draws.S;
@@ -1483,14 +1522,8 @@ static int leafspace_run(bark_ctx *ctx, const void *packed, const bark_pack_info
                                caller);
             if (rc) return rc;
         } else if (want_minv) {
-            // w = M^-1 v = V'z and M^-1 = V'V (the same kernels the dense posterior / inverse export use)
             const int R = (int)g.R;
-            if ((rc = launch_predict_reduce(p, R, R, (int)bc, nullptr, wvec, nullptr, g.L.splitk ? sw.slabs : nullptr, caller)))
-                return rc;
-            const int nct = (int)(g.L.cpad / NB);
-            hipLaunchKernelGGL(vtv_kernel, dim3(xcd_grid(nct * nct, (int)bc)), dim3(THREADS), GEMM_LDS, caller, p, nct, R,
-                               (const double *)nullptr, 1.0, 1, Minv);
-            BARK_LAUNCH_CHECK();
+            if ((rc = leafspace_minv(sw, g, (int)bc, wvec, Minv, caller))) return rc;
             if (C > 0) {
                 if ((rc = walk_one_hot(packed_c, &sub, cand, C, d, (int)g.W, ccodes, ctx->fault, caller))) return rc;
                 rc = leafspace_predict(ccodes, (int)g.W, (int)g.cpad, (int)C, wvec, Minv, R, noise + c0, scale + c0, (int)m,
@@ -1501,7 +1534,7 @@ static int leafspace_run(bark_ctx *ctx, const void *packed, const bark_pack_info
                 rc = leafspace_inverse(codes, (int)g.W, (int)g.npad, (int)N, Minv, wvec, R, y, noise + c0,
                                        use_scale ? scale + c0 : nullptr, (int)m, (int)bc,
                                        reinterpret_cast<double *>(ws + g.off_wm), kinv_out + (size_t)c0 * N * N,
-                                       kinv_y_out ? kinv_y_out + (size_t)c0 * N : nullptr, caller);
+                                       kinv_y_out ? kinv_y_out + (size_t)c0 * N : nullptr, nullptr, caller);
                 if (rc) return rc;
             }
         }
@@ -1560,6 +1593,72 @@ int bark_posterior_samples_hip(bark_ctx *ctx, const void *packed, const bark_pac
     draws.idx_out = idx_out;
     return leafspace_run(ctx, packed, info, X, N, d, y, noise, scale, BARK_MLL_INCLUDE_SCALE, cand, C, nullptr, nullptr, nullptr,
                          nullptr, nullptr, info_out, workspace, workspace_bytes, Bc, stream_, draws);
+}
+
+// The noise/scale half of the sampler step for nc chains (include/bark_hip.h): leafspace_run's MLL + inverse sequence for one
+// chunk of nc forests (the same helpers), with the Metropolis decision between the MLL and the N x N expansion, which only
+// accepted chains run.
+int bark_noise_scale_step_chains_hip(bark_ctx *ctx, double *K_inv, int64_t N, int64_t nc, const void *packed,
+                                     const bark_pack_info *info, const double *X, int64_t d, const double *y,
+                                     const double *new_noise, const double *new_scale, const double *log_q_prior,
+                                     const double *log_u, double *state, int32_t *accept_out, void *workspace,
+                                     size_t workspace_bytes, void *stream_) {
+    error_buffer()[0] = 0;
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    if (!K_inv || !packed || !info || !X || !y || !new_noise || !new_scale || !log_q_prior || !log_u || !state || !accept_out ||
+        !workspace)
+        return fail(BARK_ERR_ARG, "bark_noise_scale_step_chains_hip: null argument");
+    if (nc < 1 || nc > 64) return fail(BARK_ERR_ARG, "bark_noise_scale_step_chains_hip: 1 to 64 chains (got %lld)", (long long)nc);
+    if (info->B != nc)
+        return fail(BARK_ERR_ARG, "bark_noise_scale_step_chains_hip: %lld packed forests for %lld chains", (long long)info->B,
+                    (long long)nc);
+    const int64_t m = info->m;
+    if (N < 1 || d < 1 || N > (1 << 24) || m < 1)
+        return fail(BARK_ERR_ARG, "bark_noise_scale_step_chains_hip: bad shape N=%lld d=%lld m=%lld", (long long)N, (long long)d,
+                    (long long)m);
+    if (m > LEAF_INV_MAX_TREES)
+        return fail(BARK_ERR_ARG, "bark_noise_scale_step_chains_hip: at most %d trees (got %lld)", LEAF_INV_MAX_TREES, (long long)m);
+    if (info->max_bits < 1 || info->max_bits > 8192)
+        return fail(BARK_ERR_ARG, "bark_noise_scale_step_chains_hip: at most 8192 leaves per forest (got %lld)", (long long)info->max_bits);
+    const LeafLayout g = make_leaf_layout(N, info->max_bits, m, nc, 0, true);
+    const size_t need = bark_noise_scale_step_chains_workspace_bytes(N, info->max_bits, m, nc);
+    if (workspace_bytes < need) return fail(BARK_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(BARK_ERR_ARG, "workspace must be 256-byte aligned");
+    if ((rc = set_lds_limits())) return rc;
+    hipStream_t caller = static_cast<hipStream_t>(stream_);
+    const SweepShape sh = make_shape(g.L, g.R, 0);
+    if ((rc = ctx_events(ctx, (size_t)6 * sh.nrb + 6))) return rc;
+    Sweep sw(ctx, caller, g.L, workspace, sh, (int)m);
+    char *ws = static_cast<char *>(workspace);
+    uint32_t *codes = reinterpret_cast<uint32_t *>(ws + g.off_codes);
+    unsigned long long *planes = reinterpret_cast<unsigned long long *>(ws + g.off_planes);
+    double *yy = reinterpret_cast<double *>(ws + g.off_yy);
+    double *Minv = reinterpret_cast<double *>(ws + g.off_minv);
+    double *wvec = reinterpret_cast<double *>(ws + g.off_w);
+    double *Wm = reinterpret_cast<double *>(ws + g.off_wm);
+    size_t o = g.total;
+    double *new_mll = reinterpret_cast<double *>(ws + o);
+    o = align256(o + (size_t)nc * sizeof(double));
+    int32_t *sweep_info = reinterpret_cast<int32_t *>(ws + o);
+    o = align256(o + (size_t)nc * sizeof(int32_t));
+    double *kinv_y = reinterpret_cast<double *>(ws + o);
+    const int R = (int)g.R, bc = (int)nc;
+
+    if ((rc = leafspace_sumsq(y, (int)N, yy, caller))) return rc;
+    return sw.for_chunks(nc, nc, [&](int64_t, int64_t) -> int {
+        rc = leafspace_factor_chunk(ctx, sw, sh, g, packed, info, X, N, d, y, yy, new_noise, new_scale, true, 0, sweep_info, new_mll,
+                                    codes, planes, caller);
+        if (rc) return rc;
+        rc = noise_scale_decide(new_mll, state, new_noise, log_q_prior, log_u, sweep_info, ctx->fault, bc, accept_out, caller);
+        if (rc) return rc;
+        // w and M^-1 for every chain (R x R); the N x R and N x N passes run for accepted chains only
+        if ((rc = leafspace_minv(sw, g, bc, wvec, Minv, caller))) return rc;
+        rc = leafspace_inverse(codes, (int)g.W, (int)g.npad, (int)N, Minv, wvec, R, y, new_noise, new_scale, (int)m, bc, Wm, K_inv,
+                               kinv_y, accept_out, caller);
+        if (rc) return rc;
+        return noise_scale_state(kinv_y, y, (int)N, new_mll, accept_out, bc, state, caller);
+    });
 }
 
 // out[b] = alpha * sum_i A[b][i] * y[i] + beta * c[b]  (one wave per row; fixed order; c may be null)

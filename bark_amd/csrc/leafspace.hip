@@ -175,12 +175,16 @@ __global__ __launch_bounds__(128) void leaf_predict_kernel(const uint32_t *__res
 // Explicit inverse in leaf space:  K_s^-1 = (I - c Z M^-1 Z') / sigma2,   K_s^-1 y = (y - c Z w) / sigma2.
 // Step 1 (one wave per point i):  Wm[i][q] = sum_{a in L(i)} Minv[a][q]  (row i of Z M^-1) and zy_i = sum w_a.
 // The leaf list is decoded from the one-hot code with wave-uniform control flow (no per-lane list).
+// accept (may be null): the sampler's noise/scale step builds the inverse of accepted chains only; a workgroup of a
+// forest with accept[b] <= 0 returns before it reads or writes anything else.
 __global__ __launch_bounds__(256) void leaf_rowsum_kernel(const uint32_t *__restrict__ codes, int W, int npad, int N,
                                                           const double *__restrict__ Minv, const double *__restrict__ w,
                                                           int R, const double *__restrict__ y,
                                                           const double *__restrict__ noise, const double *__restrict__ scale,
-                                                          int m, double *__restrict__ Wm, double *__restrict__ kinv_y) {
+                                                          int m, double *__restrict__ Wm, double *__restrict__ kinv_y,
+                                                          const int32_t *__restrict__ accept) {
     const int lane = threadIdx.x & 63, b = blockIdx.y;
+    if (accept && accept[b] <= 0) return;
     const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (i >= N) return;  // no barriers below
     const double *Mb = Minv + (size_t)b * R * R;
@@ -215,12 +219,16 @@ __global__ __launch_bounds__(256) void leaf_rowsum_kernel(const uint32_t *__rest
 // Step 2 (64 x 64 tile of the output):  out[i][j] = ([i == j] - c sum_{q in L(j)} Wm[i][q]) / sigma2.
 // The leaf lists of the tile's 64 columns sit in LDS ([tree][column], conflict-free); a wave owns a row at a time,
 // so its gathers stay inside one row of Wm (R doubles, L1-resident) and the store is one 512-byte segment.
+// accept: as in leaf_rowsum_kernel (the test is the same for the whole workgroup and comes before the barrier).  `out` is
+// only written, so the noise/scale step passes the chains' resident K_inv itself.
 __global__ __launch_bounds__(256) void leaf_inverse_kernel(const uint32_t *__restrict__ codes, int W, int npad, int N,
                                                            const double *__restrict__ Wm, int R,
                                                            const double *__restrict__ noise, const double *__restrict__ scale,
-                                                           int m, double *__restrict__ out) {
+                                                           int m, double *__restrict__ out,
+                                                           const int32_t *__restrict__ accept) {
     extern __shared__ unsigned short idx[];  // [m][64]
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, b = blockIdx.z;
+    if (accept && accept[b] <= 0) return;
     const int col0 = blockIdx.x * 64, row0 = blockIdx.y * 64;
     const int j = col0 + lane;
     if (threadIdx.x < 64) {
@@ -251,6 +259,52 @@ __global__ __launch_bounds__(256) void leaf_inverse_kernel(const uint32_t *__res
     }
 }
 
+// The sampler's noise/scale proposal (bark_sampler.py:266-282) decided for every chain: the Metropolis rule of lowrank.hip's
+// decide branch on new_mll (finish_leafspace_kernel's value at the proposed noise / scale) against the chain's running state.
+//   -2  a leaf walk met an invalid categorical value (every chain of the call)
+//    0  rejected; also whenever 1e-6 + noise is not positive (new_mll is NaN whatever the sweep's pivots were) and for any
+//       NaN among the operands, which compares false
+//   -1  the sweep met a non-positive pivot of I + c Z'Z (info != 0)
+//    1  accepted
+__global__ void noise_scale_decide_kernel(const double *__restrict__ new_mll, const double *__restrict__ state,
+                                          const double *__restrict__ noise, const double *__restrict__ log_q_prior,
+                                          const double *__restrict__ log_u, const int32_t *__restrict__ info,
+                                          const int32_t *__restrict__ fault, int nc, int32_t *__restrict__ accept_out) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= nc) return;
+    int acc;
+    if (*fault) {
+        acc = -2;
+    } else if (!(1e-6 + noise[b] > 0.0)) {
+        acc = 0;
+    } else if (info[b] != 0) {
+        acc = -1;
+    } else {
+        const double cur_mll = 0.5 * (-state[2 * b] - state[2 * b + 1]);
+        const double log_alpha = log_q_prior[b] + (new_mll[b] - cur_mll);
+        acc = (log_u[b] <= log_alpha && log_u[b] <= 0.0) ? 1 : 0;
+    }
+    accept_out[b] = acc;
+}
+
+// state of the accepted chains from the rebuilt inverse: y'K^-1 y = (K^-1 y)'y in rowdot_kernel's order (one wave per
+// chain), log|K| = -2 mll - y'K^-1 y.  Rejected chains keep theirs.
+__global__ __launch_bounds__(64) void noise_scale_state_kernel(const double *__restrict__ kinv_y, const double *__restrict__ y,
+                                                               int N, const double *__restrict__ new_mll,
+                                                               const int32_t *__restrict__ accept, double *__restrict__ state) {
+    const int b = blockIdx.x;
+    if (accept[b] <= 0) return;
+    const double *row = kinv_y + (size_t)b * N;
+    double s = 0.0;
+    for (int i = threadIdx.x; i < N; i += 64) s = fma(row[i], y[i], s);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if (threadIdx.x == 0) {
+        state[2 * b] = s;
+        state[2 * b + 1] = -2.0 * new_mll[b] - s;
+    }
+}
+
 }  // namespace
 
 const void *leaf_inverse_kernel_ptr() { return reinterpret_cast<const void *>(leaf_inverse_kernel); }
@@ -266,15 +320,15 @@ int leafspace_predict(const uint32_t *ccodes, int W, int cpad, int C, const doub
 
 int leafspace_inverse(const uint32_t *codes, int W, int npad, int N, const double *Minv, const double *w, int R,
                       const double *y, const double *noise, const double *scale, int m, int bc, double *Wm, double *kinv,
-                      double *kinv_y, hipStream_t s) {
+                      double *kinv_y, const int32_t *accept, hipStream_t s) {
     if (R > 65535 || m > LEAF_INV_MAX_TREES)
         return fail(BARK_ERR_ARG, "leaf-space inverse supports at most %d trees (got m = %d, R = %d)", LEAF_INV_MAX_TREES, m, R);
     hipLaunchKernelGGL(leaf_rowsum_kernel, dim3((unsigned)((N + 3) / 4), (unsigned)bc), dim3(256), 0, s, codes, W, npad, N, Minv,
-                       w, R, y, noise, scale, m, Wm, kinv_y);
+                       w, R, y, noise, scale, m, Wm, kinv_y, accept);
     BARK_LAUNCH_CHECK();
     const unsigned tiles = (unsigned)((N + 63) / 64);
     hipLaunchKernelGGL(leaf_inverse_kernel, dim3(tiles, tiles, (unsigned)bc), dim3(256), (size_t)m * 64 * sizeof(unsigned short),
-                       s, codes, W, npad, N, Wm, R, noise, scale, m, kinv);
+                       s, codes, W, npad, N, Wm, R, noise, scale, m, kinv, accept);
     BARK_LAUNCH_CHECK();
     return BARK_OK;
 }
@@ -306,6 +360,22 @@ int leafspace_finish(const double *accum, const double *yy, const double *noise,
                      int include_2pi, double *mll, hipStream_t s) {
     hipLaunchKernelGGL(finish_leafspace_kernel, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, s, accum, yy, noise, scale, m,
                        bc, N, include_2pi, mll);
+    BARK_LAUNCH_CHECK();
+    return BARK_OK;
+}
+
+int noise_scale_decide(const double *new_mll, const double *state, const double *noise, const double *log_q_prior,
+                       const double *log_u, const int32_t *info, const int32_t *fault, int nc, int32_t *accept_out,
+                       hipStream_t s) {
+    hipLaunchKernelGGL(noise_scale_decide_kernel, dim3(1), dim3(64), 0, s, new_mll, state, noise, log_q_prior, log_u, info, fault,
+                       nc, accept_out);
+    BARK_LAUNCH_CHECK();
+    return BARK_OK;
+}
+
+int noise_scale_state(const double *kinv_y, const double *y, int N, const double *new_mll, const int32_t *accept, int nc,
+                      double *state, hipStream_t s) {
+    hipLaunchKernelGGL(noise_scale_state_kernel, dim3((unsigned)nc), dim3(64), 0, s, kinv_y, y, N, new_mll, accept, state);
     BARK_LAUNCH_CHECK();
     return BARK_OK;
 }

@@ -262,8 +262,8 @@ class ChainBatch:
     """`ChainState` for several independent chains of the sampler (bark_sampler.py:147): K_inv (nc, N, N) resident,
     the per-tree proposals of all chains evaluated by ONE library call — the chain index is a grid dimension of
     every kernel, so the call costs one launch sequence.  `sweep_trees` runs a whole sweep over the trees with the
-    Metropolis decision on the device: one read-back per sweep instead of one per tree.  The chains share X and y
-    (as in the reference)."""
+    Metropolis decision on the device: one read-back per sweep instead of one per tree; `step_noise_scale` does the same
+    for the noise/scale proposal that ends a step.  The chains share X and y (as in the reference)."""
 
     def __init__(self, K_inv, K_logdet, y):
         import torch
@@ -456,3 +456,47 @@ class ChainBatch:
         if (acc < 0).any():
             raise np.linalg.LinAlgError("Singular matrix in a tree-swap update")
         return (acc.T > 0)
+
+    def step_noise_scale(self, forests, new_noise, new_scale, log_q_prior, log_u, X, feat_types) -> np.ndarray:
+        """The noise/scale proposal of `_step_bark_sampler` (bark_sampler.py:266-282) for every chain, decided on the
+        device: forests (chains, m, node_limit) — the chains' current forests, i.e. after the caller applied the mask of
+        `sweep_trees` —, new_noise, new_scale, log_q_prior, log_u (chains,).  The MLL at the proposed values comes from the
+        R x R leaf-space system of each forest; the device accepts where log_u <= min(log_q_prior + new_mll - cur_mll, 0)
+        and rebuilds K_inv of those chains only, in place.  Returns the (chains,) boolean accept mask after ONE
+        read-back; the caller keeps noise and scale and applies the mask, as bark_sampler.py:281-282 does."""
+        import torch
+
+        lib = _lib.lib()
+        ft = _feat_types(feat_types)
+        Xd = self._points_of(X, ft)
+        nodes = _as_nodes(forests, 3)
+        if nodes.ndim != 3 or nodes.shape[0] != self.nc:
+            raise ValueError(f"forests must be (chains, m, node_limit) records of {self.nc} chains, got {nodes.shape}")
+        if nodes.shape[1] > 1280:
+            raise ValueError(f"step_noise_scale supports at most 1280 trees (got {nodes.shape[1]})")
+        vecs = []
+        for name, v in (("new_noise", new_noise), ("new_scale", new_scale), ("log_q_prior", log_q_prior), ("log_u", log_u)):
+            v = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
+            if v.shape[0] != self.nc:
+                raise ValueError(f"{name} has {v.shape[0]} entries for {self.nc} chains")
+            vecs.append(_lib.to_device(v))
+        pf = packed_forest(nodes, ft)
+        state = _lib.to_device(np.ascontiguousarray(np.stack([self.quad, self.logdet], axis=1)))
+        accept = torch.empty(self.nc, dtype=torch.int32, device=self.K_inv.device)
+        ws = _lib.workspace(int(lib.bark_noise_scale_step_chains_workspace_bytes(self.N, int(pf.info.max_bits), pf.m, self.nc)))
+        _lib.check(lib.bark_noise_scale_step_chains_hip(_lib.ctx(), _lib.ptr(self.K_inv), self.N, self.nc, _lib.ptr(pf.packed),
+                                                        pf.info_ref, _lib.ptr(Xd), Xd.shape[1], _lib.ptr(self.y),
+                                                        *(_lib.ptr(v) for v in vecs), _lib.ptr(state), _lib.ptr(accept),
+                                                        _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+        acc = accept.cpu().numpy()  # the one synchronisation of the call
+        st = state.cpu().numpy()
+        # as in sweep_trees: K_inv of the accepted chains is already rewritten, so take their state before raising
+        self.quad, self.logdet = st[:, 0].copy(), st[:, 1].copy()
+        self._pending = None
+        if (acc == -2).any():
+            _lib.check_categorical_fault()  # reads and clears the context's flag, whatever feat_types says, and raises
+            raise ValueError("categorical feature value is negative, NaN or inf")
+        if (acc < 0).any():
+            b = int(np.flatnonzero(acc < 0)[0])
+            raise np.linalg.LinAlgError(f"leaf-space system of chain {b} is not positive definite at the proposed noise / scale")
+        return acc > 0

@@ -410,6 +410,30 @@ int bark_tree_sweep_chains_hip(bark_ctx *ctx, double *K_inv, int64_t N, int64_t 
                                const double *log_u, double *state, int32_t *accept_out, void *workspace,
                                size_t workspace_bytes, void *stream);
 
+/* The other half of the sampler step — the noise/scale proposal of bark_sampler.py:266-282 — for the same nc chains, again
+ * decided on the DEVICE.  packed/info: the nc CURRENT forests (info->B == nc, after the sweep's accepted trees were copied
+ * in); new_noise, new_scale, log_q_prior, log_u: DEVICE (nc,).  Per chain b, in leaf space (one R x R sweep for all chains,
+ * as bark_kernel_inverse_leafspace_hip with Bc = nc and BARK_MLL_INCLUDE_SCALE):
+ *   new_mll = MLL of forest b at (new_noise[b], new_scale[b]);   cur_mll = 0.5 (-state[2b] - state[2b+1])
+ *   accept iff log_u[b] <= log_q_prior[b] + (new_mll - cur_mll) and log_u[b] <= 0   (a NaN compares false: rejected)
+ * accept_out (DEVICE int32, (nc,)):
+ *    1  accepted: K_inv[b] = (I - c Z M^-1 Z') / s2 written in place, state[2b] = y'K^-1 y, state[2b+1] = -2 new_mll - state[2b]
+ *    0  rejected — also whenever 1e-6 + new_noise[b] is not positive (new_mll is NaN)
+ *   -1  I + c Z'Z met a non-positive pivot (e.g. a negative proposed scale; the reference has no such check, np.linalg.inv
+ *       of a singular matrix raises LinAlgError)
+ *   -2  a leaf walk met an invalid categorical value: every chain of the call (bark_ctx_status reads and clears the flag)
+ * For every value but 1 no byte of K_inv[b] or state[b] is written, and the N x R and N x N passes of such a chain do not
+ * run (their workgroups return at once; what that saves has not been measured).  Nothing synchronises; the host reads accept_out and
+ * state once.  The caller keeps noise and scale and applies the mask.  Limits: 1 <= nc <= 64, m <= 1280 trees, R <= 8192
+ * leaves, else BARK_ERR_ARG before anything is launched.
+ * workspace >= bark_noise_scale_step_chains_workspace_bytes(N, info->max_bits, info->m, nc). */
+size_t bark_noise_scale_step_chains_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t nc);
+int bark_noise_scale_step_chains_hip(bark_ctx *ctx, double *K_inv, int64_t N, int64_t nc, const void *packed,
+                                     const bark_pack_info *info, const double *X, int64_t d, const double *y,
+                                     const double *new_noise, const double *new_scale, const double *log_q_prior,
+                                     const double *log_u, double *state, int32_t *accept_out, void *workspace,
+                                     size_t workspace_bytes, void *stream);
+
 /* quick_inverse.py:37-38  mll(K_inv, K_logdet, y) = 0.5 * (-y' K_inv y - K_logdet), on device. */
 int bark_quadform_hip(const double *K_inv, const double *y, int64_t N, double *out, void *stream);
 /* out[b] = alpha * sum_i A[b * lda + i] * y[i] + beta * c[b] for b < B (c may be NULL) — e.g. log|K_s| =
