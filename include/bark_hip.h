@@ -218,7 +218,13 @@ int bark_gram_from_leaves_hip(const uint32_t *leaf1, int64_t N, const uint32_t *
  * (1 <= Bc <= B) is the number of forests resident / factorised concurrently; B is processed in chunks of Bc.
  * info_out (device, B int32): 0, or 1-based index of the first non-positive pivot (not PD), or -3 when a device-side
  *   wait timed out (bark_device_wait), or -1 when a leaf walk
- * of the call met an invalid categorical value (see bark_ctx_status).
+ * of the call met an invalid categorical value (see bark_ctx_status).  The pivot index is LAPACK potrf's `info` of that
+ *   matrix alone, eliminated in order (only the first failure of a matrix is reported); an invalid categorical
+ *   value takes precedence: -1 replaces it in every matrix of the chunk.  A matrix with info_out[b] > 0 is swept to the end with 1.0 in the place of each non-positive
+ *   pivot: its own outputs (mll_out[b] and row b of mu_out, var_out, cov_out) are unspecified — possibly not finite —
+ *   and must not be used.  The other matrices of the call are not affected: their info_out and every one of their
+ *   outputs have the bits they have in a call where matrix b is positive definite.  The same holds for info_out of the
+ *   leaf-space entry points below (a non-positive-definite M = I_R + c Z'Z, i.e. a negative scale).
  * ------------------------------------------------------------------------------------- */
 size_t bark_mll_workspace_bytes(int64_t N, int64_t C, int64_t m, int64_t Bc);
 
