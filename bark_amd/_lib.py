@@ -97,6 +97,11 @@ SIGNATURES = {
     "bark_copy2d_hip": (ci, [vp, i64, vp, i64, i64, i64, vp]),
     "bark_tree_sweep_chains_hip": (ci, [vp, vp, i64, i64, i64, vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp,
                                         ctypes.c_size_t, vp]),
+    "bark_tree_sweep_resident_table_bytes": (ctypes.c_size_t, [i64, i64]),
+    "bark_tree_sweep_resident_table": (ci, [vp, vp, vp, i64, i64, vp]),
+    "bark_tree_sweep_resident_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64]),
+    "bark_tree_sweep_resident_hip": (ci, [vp, vp, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]),
+    "bark_tree_sweep_resident_query": (ci, [i64, i64, i64, i64, ctypes.POINTER(ci), ctypes.POINTER(i64), ctypes.POINTER(ci)]),
     "bark_noise_scale_step_chains_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64]),
     "bark_noise_scale_step_chains_hip": (ci, [vp, vp, i64, i64, vp, ctypes.POINTER(PackInfo), vp, i64, vp, vp, vp, vp, vp, vp,
                                               vp, vp, ctypes.c_size_t, vp]),

@@ -84,6 +84,38 @@ def _copy2d(dst, col0: int, src):
                                           int(src.stride(0)), int(src.shape[0]), int(src.shape[1]), _lib.stream_ptr()))
 
 
+def sweep_plan(N: int, r_max: int, d: int, *, nc: int = 1, max_nodes_bytes: int = 0) -> dict:
+    """Which instance of the one-launch sweep (`ChainBatch.sweep_trees(method="resident")`) a shape takes —
+    `bark_tree_sweep_resident_query`, the function the entry point itself launches from.  N points, at most r_max leaves per
+    [old, new] pair, d features, nc chains, max_nodes_bytes = packed bytes of the largest pair (2 * stride * 16; 0 = unknown)
+    -> {"variant": 0 unsupported | 1 K_inv in LDS | 2 K_inv through global memory (L2), "lds_bytes", "threads", "d_max": the
+    largest d whose X rows still fit LDS at this N (0 if unsupported for another reason), "reason": why not, else ""}.
+    Limits: N <= 512, 2 <= r_max <= 16, nc <= 64, max_nodes_bytes <= 2048 (64 packed nodes per tree).  The launch is sized for 16
+    leaves, so the variant depends on N and d only: 1 up to N = 128 (d <= 9 there), 2 beyond.
+    Measured against method="launches" on the MI355X (DESIGN.md section 8(1), 50 proposals, 1 and 4 chains): "resident" wins
+    1.1-1.4x only at N <= 128 with at most 8 leaves per pair; it LOSES with 9-16 leaves at every N (0.8-0.95x) and everywhere
+    beyond N = 128 (0.4-0.5x at N = 256, 0.16-0.23x at N = 512).  Keep the default outside N <= 128, <= 8 leaves.
+    No GPU needed."""
+    lib = _lib.lib()
+
+    def ask(dd):
+        v, lds, th = ctypes.c_int(0), ctypes.c_int64(0), ctypes.c_int(0)
+        rc = lib.bark_tree_sweep_resident_query(N, r_max, dd, max_nodes_bytes, ctypes.byref(v), ctypes.byref(lds), ctypes.byref(th))
+        return rc, v.value, lds.value, th.value, ("" if rc == 0 else lib.bark_last_error().decode(errors="replace"))
+
+    rc, variant, lds, threads, reason = ask(d)
+    if rc == 0 and not 1 <= nc <= 64:
+        variant, lds, threads, reason = 0, 0, 0, f"one-launch sweep: {nc} chains are outside 1..64"
+    d_max = 0
+    if ask(1)[0] == 0:  # supported at all at this N and r_max: bisect the d bound
+        lo, hi = 1, 1 << 16
+        while lo < hi:
+            mid = (lo + hi + 1) // 2
+            lo, hi = (mid, hi) if ask(mid)[0] == 0 else (lo, mid - 1)
+        d_max = lo
+    return {"variant": variant, "lds_bytes": lds, "threads": threads, "d_max": d_max, "reason": reason}
+
+
 class ChainState:
     """K_inv (N, N), log|K|, y'K_inv y and the targets y of one chain, resident in HBM."""
 
@@ -393,16 +425,25 @@ class ChainBatch:
         self.logdet = np.where(keep, logdet, self.logdet)
         self._pending = None
 
-    def sweep_trees(self, old_trees, new_trees, log_q_prior, log_u, X, feat_types, scale, m: int) -> np.ndarray:
+    def sweep_trees(self, old_trees, new_trees, log_q_prior, log_u, X, feat_types, scale, m: int,
+                    method: str = "launches") -> np.ndarray:
         """One sweep of the per-tree loop of `_step_bark_sampler` (bark_sampler.py:233-264) for every chain, decided on
         the device: old_trees / new_trees (chains, steps, node_limit) — the tree of step t and its proposal, which the
         host can draw up front because a proposal only depends on the tree it replaces (tree_proposals.py) —,
         log_q_prior and log_u (chains, steps): the proposal ratio and log of the uniform draw of bark_sampler.py:258.
         Per step the device evaluates all chains, accepts where log_u <= min(log_q_prior + new_mll - cur_mll, 0) and
         rewrites those chains' K_inv.  Returns the (chains, steps) boolean accept mask — the caller copies the accepted
-        trees into its forest, as bark_sampler.py:264 does — after ONE read-back for the whole sweep."""
+        trees into its forest, as bark_sampler.py:264 does — after ONE read-back for the whole sweep.
+
+        method="launches" (default): five or six launches per step, any N, up to 64 leaves per pair.  method="resident": the
+        whole sweep in ONE launch, one workgroup per chain with K_inv in LDS or L2 (`sweep_plan` has the limits: N <= 512,
+        <= 16 leaves per pair); same state, same decision rule, K_inv equal to rounding (it sums in another order).  It
+        reads K_inv by columns and updates (i, j) and (j, i) by the same amount, so K_inv must be exactly symmetric on entry — it
+        is after `from_forests`, it need not be after a method="launches" sweep or `step_noise_scale` — and then stays so.  Outside its limits it raises ValueError — it never falls back."""
         import torch
 
+        if method not in ("launches", "resident"):
+            raise ValueError(f"unknown method {method!r} (use 'launches' or 'resident')")
         lib = _lib.lib()
         ft = _feat_types(feat_types)
         Xd = self._points_of(X, ft)
@@ -424,6 +465,11 @@ class ChainBatch:
             sizes.append(int(infos[t].packed_bytes))
             r_old[t] = self._old_leaf_counts(old[:, t], ft)
         r_max = max(int(infos[t].max_bits) for t in range(steps))
+        if method == "resident":
+            plan = sweep_plan(self.N, r_max, int(Xd.shape[1]), nc=self.nc,
+                              max_nodes_bytes=max(2 * int(infos[t].stride) * 16 for t in range(steps)))
+            if not plan["variant"]:
+                raise ValueError(f"sweep_trees(method=\"resident\"): {plan['reason']}; use method=\"launches\"")
         if r_max > MAX_RANK:
             raise ValueError(f"sweep_trees supports at most {MAX_RANK} leaves per [old, new] pair (got {r_max}); "
                              "use propose_trees / accept for this sweep")
@@ -437,13 +483,31 @@ class ChainBatch:
         lq_d, lu_d = _lib.to_device(lq), _lib.to_device(lu)
         state = _lib.to_device(np.ascontiguousarray(np.stack([self.quad, self.logdet], axis=1)))
         accept = torch.empty((steps, self.nc), dtype=torch.int32, device=self.K_inv.device)
-        ws = self._workspace(r_max, extra=16 * self.nc)
         s_sqrtm = np.ascontiguousarray(np.sqrt(scale / m))
+        if method == "resident":
+            table = np.empty(int(lib.bark_tree_sweep_resident_table_bytes(steps, self.nc)) // 8, dtype=np.int64)
+            _lib.check(lib.bark_tree_sweep_resident_table(_lib.ptr(offsets), ctypes.cast(infos, ctypes.c_void_p), _lib.ptr(r_old),
+                                                          steps, self.nc, _lib.ptr(table)))
+            table_d, s_d = _lib.to_device(table), _lib.to_device(s_sqrtm)
+            key = ("resident", r_max)
+            ws = self._ws.get(key)
+            if ws is None:
+                nbytes = int(lib.bark_tree_sweep_resident_workspace_bytes(self.N, r_max, self.nc))
+                ws = self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.K_inv.device)
+            _lib.check(lib.bark_tree_sweep_resident_hip(_lib.ctx(), _lib.ptr(self.K_inv), self.N, self.nc, steps, _lib.ptr(packed),
+                                                        _lib.ptr(table_d), _lib.ptr(Xd), Xd.shape[1], _lib.ptr(s_d),
+                                                        _lib.ptr(self.y), _lib.ptr(lq_d), _lib.ptr(lu_d), _lib.ptr(state),
+                                                        _lib.ptr(accept), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+            return self._finish_sweep(accept, state, ft)
+        ws = self._workspace(r_max, extra=16 * self.nc)
         _lib.check(lib.bark_tree_sweep_chains_hip(_lib.ctx(), _lib.ptr(self.K_inv), self.N, self.nc, steps, _lib.ptr(packed),
                                                   _lib.ptr(offsets), ctypes.cast(infos, ctypes.c_void_p), _lib.ptr(Xd), Xd.shape[1],
                                                   _lib.ptr(r_old), _lib.ptr(s_sqrtm), _lib.ptr(self.y), _lib.ptr(lq_d),
                                                   _lib.ptr(lu_d), _lib.ptr(state), _lib.ptr(accept), _lib.ptr(ws), ws.numel(),
                                                   _lib.stream_ptr()))
+        return self._finish_sweep(accept, state, ft)
+
+    def _finish_sweep(self, accept, state, ft) -> np.ndarray:
         acc = accept.cpu().numpy()  # the one synchronisation of the sweep
         st = state.cpu().numpy()
         # the device has already rewritten K_inv for every accepted step: take the running quad / logdet that belong to

@@ -416,6 +416,40 @@ int bark_tree_sweep_chains_hip(bark_ctx *ctx, double *K_inv, int64_t N, int64_t 
                                const double *log_u, double *state, int32_t *accept_out, void *workspace,
                                size_t workspace_bytes, void *stream);
 
+/* The same sweep in ONE kernel launch for small N: one workgroup per chain keeps K_inv[b] in LDS (variant 1) or works on it in
+ * global memory, where one workgroup's matrix stays in L2 (variant 2), and loops over the steps itself — walk, Y = K_inv U in
+ * column form, the r x r system C + U'Y by elimination with partial pivoting, the decision above, the rewrite — with workgroup
+ * barriers as its only synchronisation.  Opt-in: the sums run in another order than in bark_tree_sweep_chains_hip, so K_inv
+ * agrees with that path to rounding, not bit for bit.  The rewrite gives entries (i, j) and (j, i) the same bits; K_inv must be
+ * symmetric on entry (it is read by columns).
+ * Limits: 1 <= N <= 512, 2 <= leaves per [old, new] pair <= 16, at most 64 packed nodes per tree (infos[t].stride: the pair is
+ * walked in 2 KiB of LDS; a tree of 15 leaves has 29), 1 <= nc <= 64, 0 < r_old < r, and d small enough for the X rows to sit in
+ * LDS beside the rest (N * (d | 1) * 8 bytes: d <= 9 beside K_inv at N = 128, d <= 21 at N = 512;
+ * bark_tree_sweep_resident_query answers for a shape).  Anything else: BARK_ERR_ARG before any launch — use
+ * bark_tree_sweep_chains_hip.
+ * A single kernel cannot read the per-step HOST arrays, and *_hip entry points neither allocate nor copy, so the caller builds a
+ * step table on the host and uploads it like `packed`:
+ *   bark_tree_sweep_resident_table (host -> host) validates the limits and writes int64 words: per step
+ *   {packed_offsets[t], infos[t].stride, infos[t].max_depth, infos[t].max_bits} (n_steps x 4), then r_old (n_steps x nc);
+ *   packed_offsets must be multiples of 16.
+ * state, accept_out, log_q_prior, log_u: as in bark_tree_sweep_chains_hip; s is a DEVICE array (nc,) here.  The call enqueues
+ * exactly one kernel, does not synchronise and can be captured in a hipGraph.  The launch is sized for 16 leaves per pair (the
+ * entry point sees no host copy of the steps), so the variant depends on N and d only.  workspace: bark_tree_sweep_resident_workspace_bytes bytes, not touched today. */
+size_t bark_tree_sweep_resident_table_bytes(int64_t n_steps, int64_t nc);
+int bark_tree_sweep_resident_table(const int64_t *packed_offsets, const bark_pack_info *infos, const int64_t *r_old,
+                                   int64_t n_steps, int64_t nc, void *table_host_out);
+size_t bark_tree_sweep_resident_workspace_bytes(int64_t N, int64_t r_max, int64_t nc);
+int bark_tree_sweep_resident_hip(bark_ctx *ctx, double *K_inv, int64_t N, int64_t nc, int64_t n_steps, const void *packed,
+                                 const void *table_dev, const double *X, int64_t d, const double *s_dev, const double *y,
+                                 const double *log_q_prior, const double *log_u, double *state, int32_t *accept_out,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+/* Which instance a shape takes: *variant_out = 0 unsupported (returns BARK_ERR_ARG with the reason), 1 K_inv in LDS, 2 K_inv
+ * through global memory; the launch's dynamic LDS and workgroup size.  Unsupported: N, d outside the limits above, r_max outside
+ * 2..16, max_nodes_bytes (packed bytes of the largest pair, 2 * stride * 16) above 2048.  Among the supported shapes the variant
+ * follows from N and d alone.  Pure host code: works without a GPU. */
+int bark_tree_sweep_resident_query(int64_t N, int64_t r_max, int64_t d, int64_t max_nodes_bytes, int *variant_out,
+                                   int64_t *lds_bytes_out, int *threads_out);
+
 /* The other half of the sampler step — the noise/scale proposal of bark_sampler.py:266-282 — for the same nc chains, again
  * decided on the DEVICE.  packed/info: the nc CURRENT forests (info->B == nc, after the sweep's accepted trees were copied
  * in); new_noise, new_scale, log_q_prior, log_u: DEVICE (nc,).  Per chain b, in leaf space (one R x R sweep for all chains,
