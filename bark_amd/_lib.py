@@ -102,6 +102,17 @@ SIGNATURES = {
     "bark_tree_sweep_resident_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64]),
     "bark_tree_sweep_resident_hip": (ci, [vp, vp, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]),
     "bark_tree_sweep_resident_query": (ci, [i64, i64, i64, i64, ctypes.POINTER(ci), ctypes.POINTER(i64), ctypes.POINTER(ci)]),
+    "bark_leafchain_query": (ci, [i64, i64, i64, i64, i64, i64, vp]),
+    "bark_leafchain_bytes": (ctypes.c_size_t, [i64, i64, i64, i64, i64]),
+    "bark_leafchain_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64, i64]),
+    "bark_leafchain_init_hip": (ci, [vp, vp, i64, i64, i64, i64, i64, vp, ctypes.POINTER(PackInfo), vp, vp, i64, vp, vp, vp, vp, vp,
+                                     vp, ctypes.c_size_t, vp]),
+    "bark_leafchain_sweep_table_bytes": (ctypes.c_size_t, [i64, i64]),
+    "bark_leafchain_sweep_table": (ci, [vp, vp, vp, vp, vp, i64, i64, i64, i64, i64, vp]),
+    "bark_leafchain_sweep_hip": (ci, [vp, vp, i64, i64, i64, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp,
+                                      ctypes.c_size_t, vp]),
+    "bark_leafchain_noise_scale_hip": (ci, [vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]),
+    "bark_leafchain_export_hip": (ci, [vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp]),
     "bark_noise_scale_step_chains_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64]),
     "bark_noise_scale_step_chains_hip": (ci, [vp, vp, i64, i64, vp, ctypes.POINTER(PackInfo), vp, i64, vp, vp, vp, vp, vp, vp,
                                               vp, vp, ctypes.c_size_t, vp]),

@@ -1,3 +1,4 @@
 from .mll import batched_kernel_inverse, batched_mll, mll, schedule_plan  # noqa: F401
 from . import quick_inverse  # noqa: F401
 from .incremental import ChainBatch, ChainState, sweep_plan  # noqa: F401,E402
+from .leafchain import LeafChainBatch, leafchain_plan  # noqa: F401,E402

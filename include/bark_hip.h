@@ -474,6 +474,80 @@ int bark_noise_scale_step_chains_hip(bark_ctx *ctx, double *K_inv, int64_t N, in
                                      const double *log_u, double *state, int32_t *accept_out, void *workspace,
                                      size_t workspace_bytes, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Leaf-space sampler chains — the same two halves of `_step_bark_sampler` (bark_sampler.py:233-264 the tree loop, :266-282 the
+ * noise/scale proposal) on a chain state that never holds an N x N matrix: with Z the N x R one-hot leaf matrix, s2 = 1e-6 + noise,
+ * c = scale / (m s2), M = I_R + c Z'Z and v = Z'y (the leaf-space block above), a chain keeps P = M^-1 (Rcap x Rcap), the
+ * bit-planes of its leaves, v, q = v'Pv and log|M|.  Swapping a tree removes its r_old rows and columns of M and borders in the
+ * r_new of the proposal:  O(R^2 r + R r N / 64) per proposal and about 8 Rcap^2 + Rcap N / 8 bytes per chain, whatever N is,
+ * where bark_tree_sweep_chains_hip reads (and on accept rewrites) 8 N^2 bytes.  Opt-in: cond(M) ~ N scale / s2, so the path
+ * loses digits as noise -> 0 like every leaf-space route; decisions and scalars agree with the dense
+ * sweep to the project's bars at noise >= 1e-2.
+ *
+ * state: one opaque device block of bark_leafchain_bytes(N, Rcap, m, lcap, nc) bytes, nc chains of `chain_bytes` each, written by
+ * ..._init_hip and updated in place by ..._sweep_hip / ..._noise_scale_hip; the five shape arguments must be those of init.
+ *   Rcap  slots (rows of P) per chain: the leaves of the forest plus room to grow; unused slots are identity rows of P
+ *   lcap  most leaves a tree may have (old or new)
+ * Leaves are numbered per tree in the packer's order (bark_forest_pack, depth first, left child first); leaves that no point
+ * reaches are kept (an identity row).  mstate (DEVICE, (nc, 2)): y'K_s^-1 y and log|K_s| per chain, as `state` of
+ * bark_tree_sweep_chains_hip: 0.5 (-mstate[0] - mstate[1]) is quick_inverse.mll.
+ * Limits, refused with BARK_ERR_ARG before any launch: 1 <= nc <= 64, m <= 64 trees, lcap <= 32, Rcap <= 1024, at most 64 packed
+ * nodes per tree.  A leaf walk that meets an invalid categorical value sets the context's flag (bark_ctx_status).
+ * Every ..._hip entry point enqueues ONE kernel (one workgroup per chain, workgroup barriers only), does not allocate or
+ * synchronise, and can be captured in a hipGraph.  workspace >= bark_leafchain_workspace_bytes(...) for all of them.
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+    int64_t state_bytes, chain_bytes, workspace_bytes; /* the state block, one chain of it, the scratch of a call */
+    int32_t plane_words;                                /* uint64 words per bit-plane, ceil(N / 64) */
+    int32_t workgroups, threads, launches_per_sweep;    /* launch shape of a sweep */
+    int32_t max_chains, max_trees, max_leaves, max_slots, max_nodes; /* the limits above (filled even when the shape is refused) */
+} bark_leafchain_plan;
+/* Pure host code (works without a GPU): the limits, the bytes and the launch shape for a shape; BARK_ERR_ARG with the reason. */
+int bark_leafchain_query(int64_t N, int64_t Rcap, int64_t m, int64_t lcap, int64_t nc, int64_t d, bark_leafchain_plan *out);
+size_t bark_leafchain_bytes(int64_t N, int64_t Rcap, int64_t m, int64_t lcap, int64_t nc);           /* 0: shape refused */
+size_t bark_leafchain_workspace_bytes(int64_t N, int64_t Rcap, int64_t m, int64_t lcap, int64_t nc);
+/* Initial state of every chain (bark_sampler.py:153-162 in leaf space): packed/info = the nc forests (B = nc, m trees);
+ * nleaves (DEVICE int32, (nc, m)): leaves of every tree (bark_forest_pack_info of the tree alone); noise, scale (DEVICE, (nc,)).
+ * Walks the forests, builds planes, v and M, inverts M.  info_out (DEVICE int32, (nc,)): 0, or -1 when M met a non-positive
+ * pivot (a negative scale), or -2 when the leaf table does not fit the shape (nothing else of that chain is written). */
+int bark_leafchain_init_hip(bark_ctx *ctx, void *state, int64_t N, int64_t Rcap, int64_t m, int64_t lcap, int64_t nc,
+                            const void *packed, const bark_pack_info *info, const int32_t *nleaves, const double *X, int64_t d,
+                            const double *y, const double *noise, const double *scale, double *mstate, int32_t *info_out,
+                            void *workspace, size_t workspace_bytes, void *stream);
+/* The tree loop of bark_sampler.py:233-264 for nc chains in one launch.  Step t swaps tree tree_index[t] of every chain:
+ *   packed + packed_offsets[t], infos[t]: the step's nc NEW trees (bark_forest_pack with B = nc, m = 1); the old tree's slots
+ *   are known from the tree index.  log_q_prior, log_u (DEVICE, (n_steps, nc)), accept_out (DEVICE int32, (n_steps, nc)):
+ *   as in bark_tree_sweep_chains_hip — accept iff log_u <= log_q_prior + (mll' - mll) and log_u <= 0 (a NaN compares false);
+ *   -1: P_TT or S met a non-positive pivot, the chain is latched for the rest of the sweep and not touched again.
+ * The kernel cannot read host arrays, so the caller builds a step table and uploads it like `packed`:
+ *   bark_leafchain_sweep_table (host -> host) validates the limits and writes int64 words: per step {packed_offsets[t],
+ *   infos[t].stride, infos[t].max_depth, tree_index[t]}, then r_new (n_steps x nc, leaves of each new tree).  nleaves (HOST
+ *   int32, (nc, m)) are the chains' present leaf counts: with them it checks that the free slots cover the sweep in the worst
+ *   case over the accept masks (sum over trees of the largest leaf count the tree can have <= Rcap), else BARK_ERR_ARG — the
+ *   device never overflows its slot stack.  On accept the new leaves reuse the old tree's slots, then pop free ones; a shrinking
+ *   tree pushes its leftovers. */
+size_t bark_leafchain_sweep_table_bytes(int64_t n_steps, int64_t nc);
+int bark_leafchain_sweep_table(const int64_t *packed_offsets, const bark_pack_info *infos, const int64_t *tree_index,
+                               const int64_t *r_new, const int32_t *nleaves, int64_t n_steps, int64_t nc, int64_t m, int64_t lcap,
+                               int64_t Rcap, void *table_host_out);
+int bark_leafchain_sweep_hip(bark_ctx *ctx, void *state, int64_t N, int64_t Rcap, int64_t m, int64_t lcap, int64_t nc,
+                             int64_t n_steps, const void *packed, const void *table_dev, const double *X, int64_t d,
+                             const double *y, const double *log_q_prior, const double *log_u, double *mstate,
+                             int32_t *accept_out, void *workspace, size_t workspace_bytes, void *stream);
+/* The noise/scale proposal of bark_sampler.py:266-282 from the resident planes (no walk): M at the proposed values is rebuilt in
+ * the workspace and inverted.  new_noise, new_scale, log_q_prior, log_u (DEVICE, (nc,)); rule and codes of
+ * bark_noise_scale_step_chains_hip: 1 accepted (P, log|M|, q, noise, scale and mstate replaced), 0 rejected (also whenever
+ * 1e-6 + new_noise is not positive), -1 non-positive pivot (e.g. a negative scale).  For every value but 1 nothing is written. */
+int bark_leafchain_noise_scale_hip(bark_ctx *ctx, void *state, int64_t N, int64_t Rcap, int64_t m, int64_t lcap, int64_t nc,
+                                   const double *new_noise, const double *new_scale, const double *log_q_prior,
+                                   const double *log_u, double *mstate, int32_t *accept_out, void *workspace,
+                                   size_t workspace_bytes, void *stream);
+/* Canonical view of the state (tree-major, leaves in the packer's order) — what a later predict / draw path reads
+ * (tree_gps.py:80-113 in leaf space): P_out (nc, Rcap, Rcap) = M^-1 of the chain's leaves, identity beyond them; v_out (nc, Rcap);
+ * nleaves_out (DEVICE int32, (nc, m)). */
+int bark_leafchain_export_hip(bark_ctx *ctx, const void *state, int64_t N, int64_t Rcap, int64_t m, int64_t lcap, int64_t nc,
+                              double *P_out, double *v_out, int32_t *nleaves_out, void *stream);
+
 /* quick_inverse.py:37-38  mll(K_inv, K_logdet, y) = 0.5 * (-y' K_inv y - K_logdet), on device. */
 int bark_quadform_hip(const double *K_inv, const double *y, int64_t N, double *out, void *stream);
 /* out[b] = alpha * sum_i A[b * lda + i] * y[i] + beta * c[b] for b < B (c may be NULL) — e.g. log|K_s| =
