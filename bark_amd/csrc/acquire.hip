@@ -1,0 +1,267 @@
+// Acquisition scan over candidates in leaf space (contract in include/bark_hip.h): the lower confidence bound of the forest
+// samples' posteriors, reduced over the forests and minimised over the candidates without a (B, C) intermediate.
+//
+// Per forest b (leaf-space quantities of leafspace.hip: w = M^-1 Z'y, M^-1, c = scale / (m s2)) and candidate x with the
+// leaves L(x) = a_0 < a_1 < ... (bits of its one-hot code, i.e. tree order):
+//     mu_b(x)  = c_b * sum_i w_b[a_i]
+//     var_b(x) = (scale_b / m) * ( sum_i Minv[a_i][a_i] + 2 * sum_i ( sum_{j < i} Minv[a_j][a_i] ) )
+// Only the upper triangle of M^-1 is read, m (m + 1) / 2 entries instead of leaf_predict_kernel's m^2.  Three kernels:
+//   acq_pack_kernel     upper triangle of M^-1, rows packed, followed by w: the image acq_scan_kernel stages in LDS
+//   acq_scan_kernel     one thread per candidate; the forests of the chunk in order, three running sums per candidate in
+//                       registers (sum of mu - kappa sd, of mu, of var + mu^2), kept in a (3, C) buffer between chunks
+//   acq_finish_kernel   the acquisition value per candidate and per-workgroup (value, lowest index) minima;
+//   acq_best_kernel     reduces those (no float atomics: ties go to the lowest candidate index)
+// The order of every sum is fixed (leaves in code-bit order, forests 0 .. B-1), so the result depends neither on the chunk
+// nor on the variant: the LDS and the global variant of acq_scan_kernel run the same arithmetic on the same values.
+#include "common.h"
+
+namespace bark {
+namespace {
+
+constexpr int ACQ_TILE = 256;                  // candidates per workgroup, one per thread
+constexpr size_t ACQ_LDS_MAX = 160 * 1024;     // all of a CU's LDS: one workgroup per CU
+constexpr int ACQ_MAX_TREES = 64;
+
+// Image (bc, tri + R): row a of the upper triangle of M^-1 at a (2R - a - 1) / 2 + a, i.e. entry (a, b >= a) at
+// a (2R - a - 1) / 2 + b; then w.
+__global__ __launch_bounds__(256) void acq_pack_kernel(const double *__restrict__ Minv, const double *__restrict__ w, int R,
+                                                       double *__restrict__ tab) {
+    const int a = blockIdx.x, b = blockIdx.y;
+    const size_t tri = (size_t)R * (R + 1) / 2;
+    double *dst = tab + (size_t)b * (tri + R);
+    const double *row = Minv + ((size_t)b * R + a) * R;
+    const int base = a * (2 * R - a - 1) / 2;
+    for (int c = a + threadIdx.x; c < R; c += 256) dst[base + c] = row[c];
+    if (a == 0)
+        for (int c = threadIdx.x; c < R; c += 256) dst[tri + c] = w[(size_t)b * R + c];
+}
+
+// LDS_TABLE: the forest's image sits in LDS ([tri + R] doubles) in front of the tile's leaf lists ([m][ACQ_TILE] 16-bit
+// ids, lane fastest: conflict-free); otherwise only the lists do and M^-1 / w are read from global memory.  A wave's 64
+// candidates walk the tree pairs (j, i) in lock step, so their table reads fall into the leaves(tree j) x leaves(tree i)
+// block of M^-1: for prior-sized trees a handful of distinct addresses, which the LDS broadcasts.
+// n: candidates of this slab (ccodes (bc, W, cpad) holds their codes), acc: the slab's part of the (3, C) sums, row stride
+// `astride`; first: this is the first chunk of forests (the sums start at zero).
+template <bool LDS_TABLE>
+__global__ __launch_bounds__(ACQ_TILE) void acq_scan_kernel(const uint32_t *__restrict__ ccodes, int W, int cpad, int n,
+                                                            const double *__restrict__ wvec, const double *__restrict__ Minv,
+                                                            const double *__restrict__ tab, int R,
+                                                            const double *__restrict__ noise, const double *__restrict__ scale,
+                                                            int m, int bc, double kappa, int first, double *__restrict__ acc,
+                                                            size_t astride) {
+    extern __shared__ double smem[];
+    const int tid = threadIdx.x;
+    const int c = blockIdx.x * ACQ_TILE + tid;
+    const bool active = c < n;
+    const int tri = R * (R + 1) / 2;
+    unsigned short *idx = reinterpret_cast<unsigned short *>(smem + (LDS_TABLE ? tri + R : 0)) + tid;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    if (active && !first) {
+        a0 = acc[c];
+        a1 = acc[astride + c];
+        a2 = acc[2 * astride + c];
+    }
+    for (int b = 0; b < bc; ++b) {
+        if (LDS_TABLE) {
+            __syncthreads();  // the previous forest's reads are done
+            const double *src = tab + (size_t)b * (tri + R);
+            for (int e = tid; e < tri + R; e += ACQ_TILE) smem[e] = src[e];
+        }
+        int cnt = 0;
+        if (active)
+            for (int w0 = 0; w0 < W; w0 += 8) {
+                uint32_t word[8];
+#pragma unroll
+                for (int u = 0; u < 8; ++u) word[u] = w0 + u < W ? ccodes[((size_t)b * W + w0 + u) * cpad + c] : 0u;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) {
+                    uint32_t bits = word[u];
+                    while (bits) {  // bits in increasing order: tree order
+                        const int a = 32 * (w0 + u) + __builtin_ctz(bits);
+                        if (cnt < m) idx[cnt * ACQ_TILE] = (unsigned short)(a < R ? a : R - 1);
+                        bits &= bits - 1;
+                        ++cnt;
+                    }
+                }
+            }
+        if (cnt > m) cnt = m;
+        if (LDS_TABLE) __syncthreads();
+        if (!active) continue;  // no barrier depends on what follows
+        const double *wb = LDS_TABLE ? smem + tri : wvec + (size_t)b * R;
+        const double *Mb = Minv + (size_t)b * R * R;
+        double s1 = 0.0, dg = 0.0, off = 0.0;
+        for (int i = 0; i < cnt; ++i) {
+            const int ai = idx[i * ACQ_TILE];
+            s1 += wb[ai];
+            dg += LDS_TABLE ? smem[ai * (2 * R - ai - 1) / 2 + ai] : Mb[(size_t)ai * R + ai];
+            double r = 0.0;
+#pragma unroll 4
+            for (int j = 0; j < i; ++j) {
+                const int aj = idx[j * ACQ_TILE];
+                r += LDS_TABLE ? smem[aj * (2 * R - aj - 1) / 2 + ai] : Mb[(size_t)aj * R + ai];
+            }
+            off += r;
+        }
+        const double sigma2 = 1e-6 + noise[b];
+        const double sc = scale[b];
+        const double mu = sc / ((double)m * sigma2) * s1;
+        const double var = sc / (double)m * (dg + 2.0 * off);
+        a0 += mu - kappa * sqrt(var > 0.0 ? var : 0.0);
+        a1 += mu;
+        a2 += var + mu * mu;
+    }
+    if (active) {
+        acc[c] = a0;
+        acc[astride + c] = a1;
+        acc[2 * astride + c] = a2;
+    }
+}
+
+// (value, index) minimum with ties to the lower index: associative and commutative, so any reduction tree gives the
+// result of a scan in candidate order.  NaN never wins.
+__device__ __forceinline__ void take_min(double &v, long long &i, double ov, long long oi) {
+    if (ov < v || (ov == v && oi < i)) {
+        v = ov;
+        i = oi;
+    }
+}
+
+__device__ __forceinline__ void block_min(double &v, long long &i, double *rv, long long *ri) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const double ov = __shfl_xor(v, o);
+        const long long oi = __shfl_xor(i, o);
+        take_min(v, i, ov, oi);
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        rv[wave] = v;
+        ri[wave] = i;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0)
+        for (int k = 1; k < 4; ++k) take_min(v, i, rv[k], ri[k]);
+}
+
+constexpr long long ACQ_NO_INDEX = 0x7fffffffffffffffLL;
+
+// kind 0: mean over the forests of mu - kappa sd (the reference's calculate_acqf, tests/optimization/test_optimality.py);
+// kind 1: the lower confidence bound of the moment-matched mixture (tree_gps.py:116-131)
+__global__ __launch_bounds__(256) void acq_finish_kernel(const double *__restrict__ acc, long long C, int B, double kappa,
+                                                         int kind, double *__restrict__ acq_out, double *__restrict__ part_v,
+                                                         long long *__restrict__ part_i) {
+    __shared__ double rv[4];
+    __shared__ long long ri[4];
+    const long long c = (long long)blockIdx.x * 256 + threadIdx.x;
+    double v = INFINITY;
+    long long i = ACQ_NO_INDEX;
+    if (c < C) {
+        if (kind == BARK_ACQ_LCB_MEAN) {
+            v = acc[c] / (double)B;
+        } else {
+            const double mu = acc[C + c] / (double)B;
+            const double var = acc[2 * C + c] / (double)B - mu * mu;
+            v = mu - kappa * sqrt(var > 0.0 ? var : 0.0);
+        }
+        if (acq_out) acq_out[c] = v;
+        i = c;
+    }
+    block_min(v, i, rv, ri);
+    if (threadIdx.x == 0) {
+        part_v[blockIdx.x] = v;
+        part_i[blockIdx.x] = i;
+    }
+}
+
+// one workgroup: the minimum over the partials; NaN / -1 when a forest of the call failed (info != 0) or no value is finite
+__global__ __launch_bounds__(256) void acq_best_kernel(const double *__restrict__ part_v, const long long *__restrict__ part_i,
+                                                       int nblk, const int32_t *__restrict__ info, int B,
+                                                       double *__restrict__ best, long long *__restrict__ best_i) {
+    __shared__ double rv[4];
+    __shared__ long long ri[4];
+    __shared__ int bad;
+    if (threadIdx.x == 0) bad = 0;
+    __syncthreads();
+    double v = INFINITY;
+    long long i = ACQ_NO_INDEX;
+    for (int k = threadIdx.x; k < nblk; k += 256) take_min(v, i, part_v[k], part_i[k]);
+    int mine = 0;
+    for (int b = threadIdx.x; b < B; b += 256) mine |= info[b] != 0;
+    if (mine) bad = 1;  // every writer stores the same value
+    block_min(v, i, rv, ri);
+    if (threadIdx.x == 0) {
+        const bool none = bad || i == ACQ_NO_INDEX;
+        *best = none ? NAN : v;
+        *best_i = none ? -1 : i;
+    }
+}
+
+size_t scan_lds_bytes(int64_t R, int64_t m, bool lds_table) {
+    const size_t lists = (size_t)m * ACQ_TILE * sizeof(unsigned short);
+    return (lds_table ? ((size_t)R * (R + 1) / 2 + R) * sizeof(double) : 0) + lists;
+}
+
+}  // namespace
+
+const void *acq_scan_lds_kernel_ptr() { return reinterpret_cast<const void *>(acq_scan_kernel<true>); }
+size_t acq_lds_max() { return ACQ_LDS_MAX; }
+int64_t acq_partials(int64_t C) { return (C + 255) / 256; }
+size_t acq_table_doubles(int64_t R) { return (size_t)R * (R + 1) / 2 + R; }
+
+// image of the chunk for the LDS variant
+int acq_pack(const double *Minv, const double *w, int R, int bc, double *tab, hipStream_t s) {
+    hipLaunchKernelGGL(acq_pack_kernel, dim3((unsigned)R, (unsigned)bc), dim3(256), 0, s, Minv, w, R, tab);
+    BARK_LAUNCH_CHECK();
+    return BARK_OK;
+}
+
+// variant: 1 LDS, 2 global (resolved by bark_acquisition_plan); n candidates of one slab against the bc forests of the chunk
+int acq_scan(int variant, const uint32_t *ccodes, int W, int cpad, int n, const double *wvec, const double *Minv,
+             const double *tab, int R, const double *noise, const double *scale, int m, int bc, double kappa, int first,
+             double *acc, size_t astride, hipStream_t s) {
+    const dim3 g((unsigned)((n + ACQ_TILE - 1) / ACQ_TILE));
+    if (variant == 1)
+        hipLaunchKernelGGL(acq_scan_kernel<true>, g, dim3(ACQ_TILE), scan_lds_bytes(R, m, true), s, ccodes, W, cpad, n, wvec, Minv,
+                           tab, R, noise, scale, m, bc, kappa, first, acc, astride);
+    else
+        hipLaunchKernelGGL(acq_scan_kernel<false>, g, dim3(ACQ_TILE), scan_lds_bytes(R, m, false), s, ccodes, W, cpad, n, wvec,
+                           Minv, tab, R, noise, scale, m, bc, kappa, first, acc, astride);
+    BARK_LAUNCH_CHECK();
+    return BARK_OK;
+}
+
+int acq_finish(const double *acc, int64_t C, int B, double kappa, int kind, double *acq_out, double *part_v, int64_t *part_i,
+               const int32_t *info, double *best, int64_t *best_i, hipStream_t s) {
+    const int nblk = (int)acq_partials(C);
+    hipLaunchKernelGGL(acq_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, s, acc, (long long)C, B, kappa, kind, acq_out, part_v,
+                       reinterpret_cast<long long *>(part_i));
+    BARK_LAUNCH_CHECK();
+    hipLaunchKernelGGL(acq_best_kernel, dim3(1), dim3(256), 0, s, part_v, reinterpret_cast<const long long *>(part_i), nblk, info, B,
+                       best, reinterpret_cast<long long *>(best_i));
+    BARK_LAUNCH_CHECK();
+    return BARK_OK;
+}
+
+}  // namespace bark
+
+extern "C" int bark_acquisition_plan(int64_t max_bits, int64_t m, int variant, int *variant_out, int64_t *lds_bytes_out) {
+    using namespace bark;
+    error_buffer()[0] = 0;
+    if (variant_out) *variant_out = 0;
+    if (lds_bytes_out) *lds_bytes_out = 0;
+    if (max_bits < 1 || max_bits > 8192 || m < 1 || m > ACQ_MAX_TREES)
+        return fail(BARK_ERR_ARG, "acquisition scan supports at most %d trees and 8192 leaves per forest (got m = %lld, R = %lld)",
+                    ACQ_MAX_TREES, (long long)m, (long long)max_bits);
+    if (variant < 0 || variant > 2) return fail(BARK_ERR_ARG, "acquisition scan: unknown variant %d", variant);
+    const size_t need = scan_lds_bytes(max_bits, m, true);
+    const bool fits = need <= ACQ_LDS_MAX;
+    if (variant == 1 && !fits) {
+        if (lds_bytes_out) *lds_bytes_out = (int64_t)need;
+        return fail(BARK_ERR_ARG, "acquisition scan: the LDS variant needs %zu bytes for R = %lld, m = %lld (limit %zu)", need,
+                    (long long)max_bits, (long long)m, ACQ_LDS_MAX);
+    }
+    const int v = variant ? variant : (fits ? 1 : 2);
+    if (variant_out) *variant_out = v;
+    if (lds_bytes_out) *lds_bytes_out = (int64_t)scan_lds_bytes(max_bits, m, v == 1);
+    return BARK_OK;
+}

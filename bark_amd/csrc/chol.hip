@@ -79,6 +79,16 @@ int noise_scale_state(const double *kinv_y, const double *y, int N, const double
                       double *state, hipStream_t s);
 int leafspace_finish(const double *accum, const double *yy, const double *noise, const double *scale, int m, int bc, int N,
                      int include_2pi, double *mll, hipStream_t s);
+int acq_pack(const double *Minv, const double *w, int R, int bc, double *tab, hipStream_t s);
+int acq_scan(int variant, const uint32_t *ccodes, int W, int cpad, int n, const double *wvec, const double *Minv,
+             const double *tab, int R, const double *noise, const double *scale, int m, int bc, double kappa, int first,
+             double *acc, size_t astride, hipStream_t s);
+int acq_finish(const double *acc, int64_t C, int B, double kappa, int kind, double *acq_out, double *part_v, int64_t *part_i,
+               const int32_t *info, double *best, int64_t *best_i, hipStream_t s);
+const void *acq_scan_lds_kernel_ptr();
+size_t acq_lds_max();
+int64_t acq_partials(int64_t C);
+size_t acq_table_doubles(int64_t R);
 int64_t sample_spad(int64_t S);
 int64_t sample_partials(int64_t C, int64_t S);
 int sample_weights(const double *V, long ldv, long vstride, const double *w, const double *eps, int R, int Rpad, int S,
@@ -363,6 +373,7 @@ int set_lds_limits() {
         if (e == hipSuccess) e = set(reinterpret_cast<const void *>(solve_narrow_kernel<1, 1>), GEMM_LDS);
         if (e == hipSuccess) e = set(reinterpret_cast<const void *>(solve_narrow_kernel<2, 1>), GEMM_LDS);
         if (e == hipSuccess) e = set(leaf_inverse_kernel_ptr(), LEAF_INV_LDS_MAX);
+        if (e == hipSuccess) e = set(acq_scan_lds_kernel_ptr(), acq_lds_max());
         status[dev] = (int)e;
     });
     if (status[dev] != 0)
@@ -1399,6 +1410,36 @@ size_t bark_noise_scale_step_chains_workspace_bytes(int64_t N, int64_t max_bits,
     return align256(o + (size_t)nc * N * sizeof(double));
 }
 
+// acquisition scan: the leaf-space posterior layout with the codes of one slab of candidates, then the LDS image of the
+// chunk (bc, tri + R), the running sums (3, C) and the per-workgroup minima of the finish
+struct AcqLayout {
+    LeafLayout g;
+    int64_t slab;
+    size_t off_tab, off_acc, off_part, off_part_i, total;
+};
+constexpr int64_t ACQ_SLAB = 1 << 16;  // candidates walked and scanned per launch pair: bounds the code buffer (Bc, W, slab)
+static AcqLayout make_acq_layout(int64_t N, int64_t max_bits, int64_t m, int64_t Bc, int64_t C) {
+    AcqLayout a;
+    a.slab = C < ACQ_SLAB ? C : ACQ_SLAB;
+    a.g = make_leaf_layout(N, max_bits, m, Bc, a.slab);
+    size_t o = a.g.total;
+    a.off_tab = o;
+    o = align256(o + (size_t)Bc * acq_table_doubles(max_bits) * sizeof(double));
+    a.off_acc = o;
+    o = align256(o + (size_t)3 * C * sizeof(double));
+    a.off_part = o;
+    o = align256(o + (size_t)acq_partials(C) * sizeof(double));
+    a.off_part_i = o;
+    o = align256(o + (size_t)acq_partials(C) * sizeof(int64_t));
+    a.total = o;
+    return a;
+}
+
+size_t bark_acquisition_scan_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t Bc, int64_t C) {
+    if (N < 1 || max_bits < 1 || m < 1 || Bc < 1 || C < 1) return 0;
+    return make_acq_layout(N, max_bits, m, Bc, C).total;
+}
+
 }  // extern "C"
 
 // Joint draws at the candidates (bark_posterior_samples_hip): S > 0, eps (B, S, R), and f_out (B, S, C) for
@@ -1593,6 +1634,76 @@ int bark_posterior_samples_hip(bark_ctx *ctx, const void *packed, const bark_pac
     draws.idx_out = idx_out;
     return leafspace_run(ctx, packed, info, X, N, d, y, noise, scale, BARK_MLL_INCLUDE_SCALE, cand, C, nullptr, nullptr, nullptr,
                          nullptr, nullptr, info_out, workspace, workspace_bytes, Bc, stream_, draws);
+}
+
+// Acquisition scan (include/bark_hip.h, kernels in acquire.hip): leafspace_run's posterior sequence per chunk of forests
+// (walk, I + c Z'Z, identity right-hand side, sweep, w, M^-1), consumed by acq_scan_kernel slab by slab of candidates before
+// the next chunk is prepared; the finish after the last chunk.
+int bark_acquisition_scan_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d,
+                              const double *y, const double *noise, const double *scale, const double *cand, int64_t C,
+                              double kappa, int kind, int variant, double *acq_out, double *best_out, int64_t *idx_out,
+                              int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc, void *stream_) {
+    error_buffer()[0] = 0;
+    int rc = check_ctx(ctx);
+    if (rc) return rc;
+    if (!packed || !info || !X || !y || !noise || !scale || !cand || !best_out || !idx_out || !info_out || !workspace)
+        return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: null argument");
+    const int64_t B = info->B, m = info->m;
+    if (N < 1 || d < 1 || B < 1 || Bc < 1 || C < 1 || N > (1 << 24) || C > (1 << 24))
+        return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: bad shape N=%lld d=%lld B=%lld Bc=%lld C=%lld", (long long)N,
+                    (long long)d, (long long)B, (long long)Bc, (long long)C);
+    if (kind != BARK_ACQ_LCB_MEAN && kind != BARK_ACQ_LCB_MIXTURE)
+        return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: unknown kind %d", kind);
+    if (!std::isfinite(kappa)) return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: kappa is not finite");
+    int var = 0;
+    if ((rc = bark_acquisition_plan(info->max_bits, m, variant, &var, nullptr))) return rc;
+    if (Bc > B) Bc = B;
+    if (Bc > 65535) Bc = 65535;
+    const AcqLayout a = make_acq_layout(N, info->max_bits, m, Bc, C);
+    const LeafLayout &g = a.g;
+    if (workspace_bytes < a.total) return fail(BARK_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, a.total);
+    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(BARK_ERR_ARG, "workspace must be 256-byte aligned");
+    if ((rc = set_lds_limits())) return rc;
+    hipStream_t caller = static_cast<hipStream_t>(stream_);
+    const SweepShape sh = make_shape(g.L, g.R, 0);
+    if ((rc = ctx_events(ctx, (size_t)6 * sh.nrb + 6))) return rc;
+    Sweep sw(ctx, caller, g.L, workspace, sh, (int)m);
+    char *ws = static_cast<char *>(workspace);
+    uint32_t *codes = reinterpret_cast<uint32_t *>(ws + g.off_codes);
+    unsigned long long *planes = reinterpret_cast<unsigned long long *>(ws + g.off_planes);
+    double *yy = reinterpret_cast<double *>(ws + g.off_yy);
+    uint32_t *ccodes = reinterpret_cast<uint32_t *>(ws + g.off_ccodes);
+    double *Minv = reinterpret_cast<double *>(ws + g.off_minv);
+    double *wvec = reinterpret_cast<double *>(ws + g.off_w);
+    double *tab = reinterpret_cast<double *>(ws + a.off_tab);
+    double *acc = reinterpret_cast<double *>(ws + a.off_acc);
+    const int R = (int)g.R;
+
+    if ((rc = leafspace_sumsq(y, (int)N, yy, caller))) return rc;
+    rc = sw.for_chunks(B, Bc, [&](int64_t c0, int64_t bc) -> int {
+        bark_pack_info sub = *info;
+        sub.B = bc;
+        const char *packed_c = static_cast<const char *>(packed) + (size_t)c0 * m * info->stride * 16;
+        int r = leafspace_factor_chunk(ctx, sw, sh, g, packed_c, &sub, X, N, d, y, yy, noise + c0, scale + c0, true, 0, info_out + c0,
+                                       nullptr, codes, planes, caller);
+        if (r) return r;
+        if ((r = leafspace_minv(sw, g, (int)bc, wvec, Minv, caller))) return r;
+        if (var == 1 && (r = acq_pack(Minv, wvec, R, (int)bc, tab, caller))) return r;
+        for (int64_t s0 = 0; s0 < C; s0 += a.slab) {
+            const int64_t n = C - s0 < a.slab ? C - s0 : a.slab;
+            if ((r = walk_one_hot(packed_c, &sub, cand + (size_t)s0 * d, n, d, (int)g.W, ccodes, ctx->fault, caller))) return r;
+            r = acq_scan(var, ccodes, (int)g.W, (int)bark_leaf_npad(n), (int)n, wvec, Minv, tab, R, noise + c0, scale + c0, (int)m,
+                         (int)bc, kappa, c0 == 0, acc + s0, (size_t)C, caller);
+            if (r) return r;
+        }
+        hipLaunchKernelGGL(fault_info_kernel, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, caller, ctx->fault, sw.p.info,
+                           (int)bc);
+        BARK_LAUNCH_CHECK();
+        return BARK_OK;
+    });
+    if (rc) return rc;
+    return acq_finish(acc, C, (int)B, kappa, kind, acq_out, reinterpret_cast<double *>(ws + a.off_part),
+                      reinterpret_cast<int64_t *>(ws + a.off_part_i), info_out, best_out, idx_out, caller);
 }
 
 // The noise/scale half of the sampler step for nc chains (include/bark_hip.h): leafspace_run's MLL + inverse sequence for one

@@ -343,6 +343,44 @@ int bark_posterior_samples_hip(bark_ctx *ctx, const void *packed, const bark_pac
                                void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Acquisition scan: the lower confidence bound of the forest samples' posteriors over C candidates and its minimiser, in
+ * the same leaf space, without the (B, C) arrays of mu and var (the reference's end-to-end test defines the acquisition,
+ * tests/optimization/test_optimality.py:60-63: acqf(x) = mean_b(mu_b(x) - kappa sqrt(var_b(x))); its proposal must not be
+ * worse than the minimum of acqf over random candidates).  With L(x) = a_0 < a_1 < ... the bits of candidate x's one-hot
+ * code (one leaf per tree, in tree order) and w_b, M_b^-1, c_b as above:
+ *   mu_b(x)  = c_b sum_i w_b[a_i]
+ *   var_b(x) = (scale_b / m) ( sum_i (M_b^-1)[a_i][a_i] + 2 sum_i ( sum_{j<i} (M_b^-1)[a_j][a_i] ) )
+ * (the quadratic form of leaf_predict over the upper triangle: m (m + 1) / 2 reads instead of m^2).  Per candidate three
+ * sums run over the forests: sum_b (mu_b - kappa sqrt(max(var_b, 0))), sum_b mu_b and sum_b (var_b + mu_b^2).
+ *   kind = BARK_ACQ_LCB_MEAN:     acq[x] = (1/B) sum_b (mu_b - kappa sd_b)
+ *   kind = BARK_ACQ_LCB_MIXTURE:  acq[x] = mu_mix - kappa sqrt(max(var_mix, 0)),  mu_mix = (1/B) sum_b mu_b,
+ *                                 var_mix = (1/B) sum_b (var_b + mu_b^2) - mu_mix^2        (tree_gps.py:116-131)
+ * best_out / idx_out: the minimum of acq over the candidates and its index (ties: the lowest index); acq_out: (C,) or NULL.
+ * If any info_out[b] != 0 (non-positive-definite M: k > 0; invalid categorical value: -1) they are NaN and -1.
+ * Summation order (part of the contract): leaves in code-bit order within a candidate as written above, forests strictly
+ * b = 0 .. B-1 across chunks.  The result therefore depends neither on Bc nor on the variant, bit for bit.
+ * variant: 0 auto, 1 the forest's packed upper triangle of M^-1 and w staged in LDS (R (R + 1) / 2 + R doubles beside the
+ * leaf lists of the workgroup's 256 candidates, m x 256 16-bit ids, in the 160 KiB of a CU), 2 the same arithmetic with
+ * M^-1 and w read from global memory; auto takes 1 where it fits.  bark_acquisition_plan answers which one a shape takes
+ * (*variant_out) and the dynamic LDS of that launch (*lds_bytes_out; for a refused variant = 1 the bytes it would need);
+ * it and the workspace query are pure host code.
+ * Limits, refused with BARK_ERR_ARG before any launch: m <= 64 trees, R <= 8192 leaves, 1 <= C <= 2^24, unknown kind or
+ * variant, variant = 1 where the LDS does not hold the table, kappa not finite.  The call only enqueues (no allocation, no
+ * host synchronisation).  Extra memory: the leaf-space posterior workspace of one chunk with the codes of at most 65536
+ * candidates at a time, Bc (R (R + 1) / 2 + R) doubles, and 3 C + C / 128 doubles.
+ * ------------------------------------------------------------------------------------- */
+#define BARK_ACQ_LCB_MEAN 0
+#define BARK_ACQ_LCB_MIXTURE 1
+size_t bark_acquisition_scan_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t Bc, int64_t C);
+int bark_acquisition_plan(int64_t max_bits, int64_t m, int variant /* 0 auto, 1 LDS, 2 global */, int *variant_out,
+                          int64_t *lds_bytes_out);
+int bark_acquisition_scan_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d,
+                              const double *y, const double *noise, const double *scale, const double *cand, int64_t C,
+                              double kappa, int kind, int variant, double *acq_out /* (C,) or NULL */, double *best_out /* 1 */,
+                              int64_t *idx_out /* 1 */, int32_t *info_out /* (B,) */, void *workspace, size_t workspace_bytes,
+                              int64_t Bc, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Woodbury / determinant-lemma updates — quick_inverse.py:13-33 (the per-tree step of the sampler,
  * bark_sampler.py:233-257).  With mul = -1 if `subtract` else +1:
  *   K_out         = K_inv - K_inv U (mul I + U' K_inv U)^-1 U' K_inv          (low_rank_inv_update)
