@@ -48,10 +48,14 @@
 // D reg v: row = (l>>4) + 4v, col = l&15.  Both GEMM operands are "k-major" panels of U (rows = k,
 // 128 contiguous columns), so a panel row is one 1 KiB coalesced wave load and the LDS image
 // As[k][128(+16 pad)] is read conflict-free by ds_read_b64 (row stride 1152 B == 128 mod 256).
+//
+// The last part of the file is the host side of the leaf-space entry points (LeafSystem): they run this sweep on the R x R
+// system I + c Z'Z and need Sweep and the kernels above; their own kernels are in leafspace.hip, sample.hip, acquire.hip.
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
 #include <mutex>
+#include <optional>
 #include <type_traits>
 #include <vector>
 
@@ -1336,282 +1340,314 @@ int bark_mll_batched_hip(bark_ctx *ctx, const void *packed, const bark_pack_info
     return BARK_OK;
 }
 
+}  // extern "C"
+
 // ---------------------------------------------------------------------------------------------
-// Leaf-space MLL (kernels in leafspace.hip): factorises I_R + c Z'Z (R x R) instead of K_s (N x N).
+// Leaf-space calls (kernels in leafspace.hip, sample.hip, acquire.hip): they factorise I_R + c Z'Z (R x R) instead of
+// K_s (N x N).  LeafSystem is the host side all of them share: one workspace layout (leaf_areas), one opening sequence and the
+// per-chunk steps.  An entry point checks its own arguments, says what it keeps in the workspace (LeafNeeds), opens the
+// system and hands for_chunks a body that lists the steps it takes.
 // ---------------------------------------------------------------------------------------------
-struct LeafLayout {
-    Layout L;         // the R x R sweep workspace (N := R; candidates := R identity columns for the posterior)
-    int64_t R, Rpad, W, npad, Q, cpad, Spad;
-    size_t off_codes, off_planes, off_yy, off_ccodes, off_minv, off_w, off_wm, off_wt, off_part, off_part_i, total;
+namespace {
+
+// what a call keeps in its workspace besides the R x R sweep's own areas, the leaf codes of the N points and y'y
+struct LeafNeeds {
+    int64_t cand = 0;         // candidate columns whose one-hot codes are resident at a time
+    bool identity = false;    // R identity columns appended to the sweep: it also yields V = U^-T, hence w = M^-1 v = V'z
+    bool minv = false;        // ... and M^-1 = V'V itself (Bc, R, R)
+    bool rowsum = false;      // the (Bc, N, R) row-sum scratch of the N x N expansion
+    int64_t S = 0;            // S joint draws at the `cand` candidates: Wt (Bc, Rpad, Spad) and the partials of their max / min
+    int64_t scan = 0;         // acquisition scan over this many candidates: LDS image (Bc, tri + R), running sums (3, scan) and
+                              // the per-workgroup minima of the finish
+    bool chain_step = false;  // noise/scale step: new_mll and the sweep's info (Bc each), K^-1 y (Bc, N)
 };
 
-// C > 0: posterior at C candidates; want_inverse: explicit K_s^-1.  Either needs M^-1 (identity columns in the sweep).
-// S > 0 (with C > 0): S joint draws at the candidates instead, which need V = U^-T and w but not M^-1 itself.
-static LeafLayout make_leaf_layout(int64_t N, int64_t max_bits, int64_t m, int64_t Bc, int64_t C = 0,
-                                   bool want_inverse = false, int64_t S = 0) {
-    LeafLayout g;
-    const bool want_minv = C > 0 || want_inverse;
-    const bool sampling = S > 0;
-    g.R = max_bits;
-    g.Rpad = round_up(max_bits, NB);
-    g.W = (max_bits + 31) / 32;
-    g.npad = round_up(N, NB);
-    g.Q = g.npad / 64;
-    g.L = make_layout(max_bits, want_minv ? max_bits : 0, m, Bc);
-    g.cpad = C > 0 ? round_up(C, NB) : 0;
-    size_t o = g.L.total;
-    g.off_codes = o;
-    o = align256(o + (size_t)Bc * g.W * g.npad * sizeof(uint32_t));
-    g.off_planes = o;
-    o = align256(o + (size_t)Bc * 32 * g.W * g.Q * sizeof(unsigned long long));
-    g.off_yy = o;
-    o = align256(o + 64);
-    g.off_ccodes = o;
-    o = align256(o + (size_t)Bc * g.W * g.cpad * sizeof(uint32_t));
-    g.off_minv = o;
-    if (want_minv && !sampling) o = align256(o + (size_t)Bc * max_bits * max_bits * sizeof(double));
-    g.off_w = o;
-    if (want_minv) o = align256(o + (size_t)Bc * max_bits * sizeof(double));
-    g.off_wm = o;
-    if (want_inverse) o = align256(o + (size_t)Bc * N * max_bits * sizeof(double));
-    g.Spad = sampling ? sample_spad(S) : 0;
-    g.off_wt = o;
-    if (sampling) o = align256(o + (size_t)Bc * g.Rpad * g.Spad * sizeof(double));
-    g.off_part = o;
-    if (sampling) o = align256(o + (size_t)Bc * sample_partials(C, S) * sizeof(double));
-    g.off_part_i = o;
-    if (sampling) o = align256(o + (size_t)Bc * sample_partials(C, S) * sizeof(int64_t));
-    g.total = o;
-    return g;
+// 256-byte aligned areas handed out front to back; base == nullptr: sizes only
+struct Carve {
+    char *base;
+    size_t o = 0;
+    template <class T> T *take(size_t n) {
+        T *p = base ? reinterpret_cast<T *>(base + o) : nullptr;
+        o = align256(o + n * sizeof(T));
+        return p;
+    }
+};
+
+struct LeafAreas {
+    Layout L;  // the R x R sweep workspace (N := R; candidates := the R identity columns), at the front
+    int64_t R, Rpad, W, npad, cpad, Spad;
+    uint32_t *codes, *ccodes;    // one-hot leaf codes of the N points / of the resident candidates (Bc, W, npad | cpad)
+    unsigned long long *planes;  // bit planes of `codes` (Bc, 32 W, npad / 64)
+    double *yy;                  // y'y
+    double *Minv, *w, *Wm, *Wt;  // see LeafNeeds; an area the call does not need is empty
+    double *tab, *acc;           // acquisition scan
+    double *part;                // (value, index) partial results: of the draws' max / min, or of the scan's finish
+    int64_t *part_i;
+    double *new_mll, *kinv_y;  // noise/scale step
+    int32_t *sweep_info;
+    size_t total;
+};
+
+// The whole workspace of a leaf-space call with Bc forests resident.  Every *_workspace_bytes function and every entry point
+// gets its sizes and pointers here, so the two cannot disagree.
+LeafAreas leaf_areas(void *workspace, int64_t N, int64_t R, int64_t m, int64_t Bc, const LeafNeeds &q) {
+    LeafAreas a;
+    a.R = R;
+    a.Rpad = round_up(R, NB);
+    a.W = (R + 31) / 32;
+    a.npad = round_up(N, NB);
+    a.cpad = q.cand > 0 ? round_up(q.cand, NB) : 0;
+    a.Spad = q.S > 0 ? sample_spad(q.S) : 0;
+    a.L = make_layout(R, q.identity ? R : 0, m, Bc);
+    const size_t nb = (size_t)Bc;
+    const size_t partials = nb * (q.S > 0 ? sample_partials(q.cand, q.S) : 0) + acq_partials(q.scan);
+    Carve cv{static_cast<char *>(workspace), a.L.total};
+    a.codes = cv.take<uint32_t>(nb * a.W * a.npad);
+    a.planes = cv.take<unsigned long long>(nb * 32 * a.W * (a.npad / 64));
+    a.yy = cv.take<double>(8);
+    a.ccodes = cv.take<uint32_t>(nb * a.W * a.cpad);
+    a.Minv = cv.take<double>(q.minv ? nb * R * R : 0);
+    a.w = cv.take<double>(q.identity ? nb * R : 0);
+    a.Wm = cv.take<double>(q.rowsum ? nb * N * R : 0);
+    a.Wt = cv.take<double>(nb * a.Rpad * a.Spad);
+    a.tab = cv.take<double>(q.scan > 0 ? nb * acq_table_doubles(R) : 0);
+    a.acc = cv.take<double>((size_t)3 * q.scan);
+    a.part = cv.take<double>(partials);
+    a.part_i = cv.take<int64_t>(partials);
+    a.new_mll = cv.take<double>(q.chain_step ? nb : 0);
+    a.sweep_info = cv.take<int32_t>(q.chain_step ? nb : 0);
+    a.kinv_y = cv.take<double>(q.chain_step ? nb * N : 0);
+    a.total = cv.o;
+    return a;
 }
+
+constexpr int64_t ACQ_SLAB = 1 << 16;  // candidates walked and scanned per launch pair: bounds the code buffer (Bc, W, slab)
+
+LeafNeeds mll_needs(int64_t C) {  // MLL; posterior at C candidates from w and M^-1
+    LeafNeeds q;
+    q.cand = C;
+    q.identity = q.minv = C > 0;
+    return q;
+}
+LeafNeeds inverse_needs() {  // explicit K_s^-1 = (I - c Z M^-1 Z') / sigma2
+    LeafNeeds q;
+    q.identity = q.minv = q.rowsum = true;
+    return q;
+}
+LeafNeeds samples_needs(int64_t C, int64_t S) {  // draws need V and w, not M^-1 itself
+    LeafNeeds q;
+    q.cand = C;
+    q.identity = true;
+    q.S = S;
+    return q;
+}
+LeafNeeds scan_needs(int64_t C) {  // the posterior's areas with the codes of one slab of candidates
+    LeafNeeds q = mll_needs(C < ACQ_SLAB ? C : ACQ_SLAB);
+    q.scan = C;
+    return q;
+}
+LeafNeeds chain_step_needs() {
+    LeafNeeds q = inverse_needs();
+    q.chain_step = true;
+    return q;
+}
+
+struct LeafSystem {
+    bark_ctx *ctx = nullptr;
+    hipStream_t caller = nullptr;
+    const void *packed = nullptr;
+    const bark_pack_info *info = nullptr;
+    const double *X = nullptr, *y = nullptr;
+    int64_t N = 0, d = 0, B = 0, Bc = 0;
+    int m = 0, R = 0, W = 0;
+    bool identity = false;
+    LeafAreas a{};
+    SweepShape sh;
+    std::optional<Sweep> sw;
+    // the current chunk (for_chunks): its forests, and how many
+    bark_pack_info sub{};
+    const char *packed_c = nullptr;
+    int bc = 0;
+
+    // Everything the entry points have in common up to the first chunk: the checks (nothing is launched before a refusal;
+    // `name` is the entry point's, for the messages), the layout for at most Bc resident forests, the sweep, and y'y.
+    // C: the entry point's candidate count (0: none), for the range check only.
+    int open(const char *name, bark_ctx *ctx_, const void *packed_, const bark_pack_info *info_, const double *X_, int64_t N_,
+             int64_t d_, const double *y_, const double *noise, const void *info_out, void *workspace, size_t workspace_bytes,
+             int64_t Bc_, int64_t C, const LeafNeeds &needs, void *stream) {
+        int rc = check_ctx(ctx_);
+        if (rc) return rc;
+        if (!packed_ || !info_ || !X_ || !y_ || !noise || !info_out || !workspace) return fail(BARK_ERR_ARG, "%s: null argument", name);
+        ctx = ctx_, packed = packed_, info = info_, X = X_, y = y_, N = N_, d = d_, B = info->B, Bc = Bc_;
+        if (N < 1 || d < 1 || B < 1 || info->m < 1 || Bc < 1 || C < 0 || N > (1 << 24) || C > (1 << 24))
+            return fail(BARK_ERR_ARG, "%s: bad shape N=%lld d=%lld B=%lld m=%lld Bc=%lld C=%lld", name, (long long)N, (long long)d,
+                        (long long)B, (long long)info->m, (long long)Bc, (long long)C);
+        if (info->max_bits < 1 || info->max_bits > 8192)
+            return fail(BARK_ERR_ARG, "%s: the leaf-space path supports at most 8192 leaves per forest (got %lld)", name,
+                        (long long)info->max_bits);
+        if (Bc > B) Bc = B;
+        if (Bc > 65535) Bc = 65535;
+        m = (int)info->m, R = (int)info->max_bits, identity = needs.identity;
+        a = leaf_areas(workspace, N, R, m, Bc, needs);
+        W = (int)a.W;
+        if (workspace_bytes < a.total) return fail(BARK_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, a.total);
+        if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(BARK_ERR_ARG, "workspace must be 256-byte aligned");
+        if ((rc = set_lds_limits())) return rc;
+        caller = static_cast<hipStream_t>(stream);
+        // the R x R sweep: N := R points, no leaf codes (A is filled by leafspace_prepare)
+        sh = make_shape(a.L, R, 0);
+        if ((rc = ctx_events(ctx, (size_t)6 * sh.nrb + 6))) return rc;
+        sw.emplace(ctx, caller, a.L, workspace, sh, m);
+        return leafspace_sumsq(y, (int)N, a.yy, caller);
+    }
+
+    // body(c0) for each chunk of at most Bc forests, c0 its first forest; sub / packed_c / bc describe it to the steps below
+    template <class F> int for_chunks(F &&body) {
+        return sw->for_chunks(B, Bc, [&](int64_t c0, int64_t n) -> int {
+            sub = *info;
+            sub.B = n;
+            bc = (int)n;
+            packed_c = static_cast<const char *>(packed) + (size_t)c0 * m * info->stride * 16;
+            return body(c0);
+        });
+    }
+
+    // leaf walk, I + c Z'Z and v = Z'y, the identity right-hand side when the call needs it, the R x R sweep and, with `mll`,
+    // the MLL.  noise / scale / info_out / mll: the chunk's.  `info_out` receives the sweep's pivot status.
+    int factor_chunk(const double *noise, const double *scale, int32_t *info_out, double *mll, int include_2pi) {
+        Mats &p = sw->p;
+        int rc;
+        sw->configure(plan_chunk(sh, bc, false, false, sw->panel != sw->main, SweepPath::LeafSpace), bc);
+        p.info = info_out;
+        if ((rc = walk_one_hot(packed_c, &sub, X, N, d, W, a.codes, ctx->fault, caller))) return rc;
+        rc = leafspace_prepare(a.codes, W, (int)a.npad, a.planes, R, (int)a.Rpad, noise, scale, m, bc, p.A, p.ld, p.bstride, y, (int)N,
+                               p.yz, p.accum, p.info, caller);
+        if (rc) return rc;
+        if (identity) {
+            dim3 gi((unsigned)((a.L.cpad + 255) / 256), (unsigned)a.L.npad, (unsigned)bc);
+            hipLaunchKernelGGL(identity_rhs_kernel, gi, dim3(256), 0, caller, p, R, (int)a.L.cpad);
+            BARK_LAUNCH_CHECK();
+        }
+        if ((rc = sw->factor())) return rc;
+        if (mll) return leafspace_finish(p.accum, a.yy, noise, scale, m, bc, (int)N, include_2pi, mll, caller);
+        return BARK_OK;
+    }
+
+    // w = M^-1 v = V'z from the swept chunk (the kernel of the dense posterior mean)
+    int solve_w() {
+        return launch_predict_reduce(sw->p, R, R, bc, nullptr, a.w, nullptr, a.L.splitk ? sw->slabs : nullptr, caller);
+    }
+    // ... and M^-1 = V'V (the kernel of the dense inverse export)
+    int solve_w_minv() {
+        const int rc = solve_w();
+        if (rc) return rc;
+        const int nct = (int)(a.L.cpad / NB);
+        hipLaunchKernelGGL(vtv_kernel, dim3(xcd_grid(nct * nct, bc)), dim3(THREADS), GEMM_LDS, caller, sw->p, nct, R,
+                           (const double *)nullptr, 1.0, 1, a.Minv);
+        BARK_LAUNCH_CHECK();
+        return BARK_OK;
+    }
+    // one-hot codes of n candidates (at most LeafNeeds::cand) under the chunk's forests -> a.ccodes
+    int walk_candidates(const double *cand, int64_t n) {
+        return walk_one_hot(packed_c, &sub, cand, n, d, W, a.ccodes, ctx->fault, caller);
+    }
+    // an invalid categorical value met by one of the chunk's walks goes into its forests' info
+    int close_chunk() {
+        hipLaunchKernelGGL(fault_info_kernel, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, caller, ctx->fault, sw->p.info, bc);
+        BARK_LAUNCH_CHECK();
+        return BARK_OK;
+    }
+};
+
+}  // namespace
+
+extern "C" {
 
 size_t bark_kernel_inverse_leafspace_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t Bc) {
     if (N < 1 || max_bits < 1 || m < 1 || Bc < 1) return 0;
-    return make_leaf_layout(N, max_bits, m, Bc, 0, true).total;
+    return leaf_areas(nullptr, N, max_bits, m, Bc, inverse_needs()).total;
 }
 
 size_t bark_mll_leafspace_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t Bc, int64_t C) {
     if (N < 1 || max_bits < 1 || m < 1 || Bc < 1 || C < 0) return 0;
-    return make_leaf_layout(N, max_bits, m, Bc, C).total;
+    return leaf_areas(nullptr, N, max_bits, m, Bc, mll_needs(C)).total;
 }
 
 size_t bark_posterior_samples_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t Bc, int64_t C, int64_t S) {
     if (N < 1 || max_bits < 1 || m < 1 || Bc < 1 || C < 1 || S < 1) return 0;
-    return make_leaf_layout(N, max_bits, m, Bc, C, false, S).total;
+    return leaf_areas(nullptr, N, max_bits, m, Bc, samples_needs(C, S)).total;
 }
 
-// noise/scale step: the leaf-space inverse layout of one chunk of nc forests, then new_mll (nc), the sweep's info (nc) and
-// K^-1 y (nc, N)
 size_t bark_noise_scale_step_chains_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t nc) {
     if (N < 1 || max_bits < 1 || m < 1 || nc < 1) return 0;
-    size_t o = make_leaf_layout(N, max_bits, m, nc, 0, true).total;
-    o = align256(o + (size_t)nc * sizeof(double));
-    o = align256(o + (size_t)nc * sizeof(int32_t));
-    return align256(o + (size_t)nc * N * sizeof(double));
-}
-
-// acquisition scan: the leaf-space posterior layout with the codes of one slab of candidates, then the LDS image of the
-// chunk (bc, tri + R), the running sums (3, C) and the per-workgroup minima of the finish
-struct AcqLayout {
-    LeafLayout g;
-    int64_t slab;
-    size_t off_tab, off_acc, off_part, off_part_i, total;
-};
-constexpr int64_t ACQ_SLAB = 1 << 16;  // candidates walked and scanned per launch pair: bounds the code buffer (Bc, W, slab)
-static AcqLayout make_acq_layout(int64_t N, int64_t max_bits, int64_t m, int64_t Bc, int64_t C) {
-    AcqLayout a;
-    a.slab = C < ACQ_SLAB ? C : ACQ_SLAB;
-    a.g = make_leaf_layout(N, max_bits, m, Bc, a.slab);
-    size_t o = a.g.total;
-    a.off_tab = o;
-    o = align256(o + (size_t)Bc * acq_table_doubles(max_bits) * sizeof(double));
-    a.off_acc = o;
-    o = align256(o + (size_t)3 * C * sizeof(double));
-    a.off_part = o;
-    o = align256(o + (size_t)acq_partials(C) * sizeof(double));
-    a.off_part_i = o;
-    o = align256(o + (size_t)acq_partials(C) * sizeof(int64_t));
-    a.total = o;
-    return a;
+    return leaf_areas(nullptr, N, max_bits, m, nc, chain_step_needs()).total;
 }
 
 size_t bark_acquisition_scan_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t Bc, int64_t C) {
     if (N < 1 || max_bits < 1 || m < 1 || Bc < 1 || C < 1) return 0;
-    return make_acq_layout(N, max_bits, m, Bc, C).total;
+    return leaf_areas(nullptr, N, max_bits, m, Bc, scan_needs(C)).total;
 }
-
-}  // extern "C"
-
-// Joint draws at the candidates (bark_posterior_samples_hip): S > 0, eps (B, S, R), and f_out (B, S, C) for
-// BARK_SAMPLE_FULL or red_out / idx_out (B, S) for BARK_SAMPLE_MAX / MIN.
-struct LeafDraws {
-    const double *eps = nullptr;
-    int64_t S = 0;
-    int reduce = BARK_SAMPLE_FULL;
-    double *f_out = nullptr, *red_out = nullptr;
-    int64_t *idx_out = nullptr;
-};
-
-// One chunk of the leaf-space system, shared by leafspace_run and the noise/scale step (sub->B forests): leaf walk, I + c Z'Z and
-// v = Z'y, the identity right-hand side when M^-1 is wanted (the sweep then also yields V = U^-T), the R x R sweep and, with
-// `mll`, the MLL.  `info` receives the sweep's pivot status.
-static int leafspace_factor_chunk(bark_ctx *ctx, Sweep &sw, const SweepShape &sh, const LeafLayout &g, const void *packed_c,
-                                  const bark_pack_info *sub, const double *X, int64_t N, int64_t d, const double *y,
-                                  const double *yy, const double *noise, const double *scale, bool want_minv, int include_2pi,
-                                  int32_t *info, double *mll, uint32_t *codes, unsigned long long *planes, hipStream_t caller) {
-    const int bc = (int)sub->B, m = (int)sub->m;
-    Mats &p = sw.p;
-    int rc;
-    sw.configure(plan_chunk(sh, bc, false, false, sw.panel != sw.main, SweepPath::LeafSpace), bc);
-    p.info = info;
-    if ((rc = walk_one_hot(packed_c, sub, X, N, d, (int)g.W, codes, ctx->fault, caller))) return rc;
-    rc = leafspace_prepare(codes, (int)g.W, (int)g.npad, planes, (int)g.R, (int)g.Rpad, noise, scale, m, bc, p.A, p.ld, p.bstride, y,
-                           (int)N, p.yz, p.accum, p.info, caller);
-    if (rc) return rc;
-    if (want_minv) {
-        dim3 gi((unsigned)((g.L.cpad + 255) / 256), (unsigned)g.L.npad, (unsigned)bc);
-        hipLaunchKernelGGL(identity_rhs_kernel, gi, dim3(256), 0, caller, p, (int)g.R, (int)g.L.cpad);
-        BARK_LAUNCH_CHECK();
-    }
-    if ((rc = sw.factor())) return rc;
-    if (mll) return leafspace_finish(p.accum, yy, noise, scale, m, bc, (int)N, include_2pi, mll, caller);
-    return BARK_OK;
-}
-
-// w = M^-1 v = V'z and M^-1 = V'V from the swept chunk (the same kernels the dense posterior / inverse export use)
-static int leafspace_minv(Sweep &sw, const LeafLayout &g, int bc, double *wvec, double *Minv, hipStream_t caller) {
-    const int R = (int)g.R;
-    int rc = launch_predict_reduce(sw.p, R, R, bc, nullptr, wvec, nullptr, g.L.splitk ? sw.slabs : nullptr, caller);
-    if (rc) return rc;
-    const int nct = (int)(g.L.cpad / NB);
-    hipLaunchKernelGGL(vtv_kernel, dim3(xcd_grid(nct * nct, bc)), dim3(THREADS), GEMM_LDS, caller, sw.p, nct, R,
-                       (const double *)nullptr, 1.0, 1, Minv);
-    BARK_LAUNCH_CHECK();
-    return BARK_OK;
-}
-
-// shared driver of the leaf-space entry points: MLL (unless mll_out is null and draws are asked for); posterior when C > 0;
-// explicit inverse when kinv_out; joint draws at the candidates when draws.S > 0
-static int leafspace_run(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d,
-                         const double *y, const double *noise, const double *scale, int flags, const double *cand,
-                         int64_t C, double *mll_out, double *mu_out, double *var_out, double *kinv_out,
-                         double *kinv_y_out, int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc,
-                         void *stream_, const LeafDraws &draws = LeafDraws()) {
-    error_buffer()[0] = 0;
-    int rc = check_ctx(ctx);
-    if (rc) return rc;
-    const bool sampling = draws.S > 0;
-    if (!packed || !info || !X || !y || !noise || (!mll_out && !sampling) || !info_out || !workspace)
-        return fail(BARK_ERR_ARG, "leaf-space entry: null argument");
-    const int64_t B = info->B, m = info->m;
-    if (N < 1 || d < 1 || B < 1 || Bc < 1 || C < 0 || N > (1 << 24) || C > (1 << 24))
-        return fail(BARK_ERR_ARG, "bark_mll_leafspace_hip: bad shape N=%lld d=%lld B=%lld Bc=%lld C=%lld", (long long)N,
-                    (long long)d, (long long)B, (long long)Bc, (long long)C);
-    if (C > 0 && (!cand || (!sampling && (!mu_out || !var_out)) || !scale || !(flags & BARK_MLL_INCLUDE_SCALE)))
-        return fail(BARK_ERR_ARG, "leaf-space posterior needs cand, mu_out, var_out, scale and BARK_MLL_INCLUDE_SCALE");
-    if ((flags & BARK_MLL_INCLUDE_SCALE) && !scale) return fail(BARK_ERR_ARG, "BARK_MLL_INCLUDE_SCALE without scale");
-    if (flags & BARK_MLL_RHS_IDENTITY) return fail(BARK_ERR_ARG, "leaf-space path computes the MLL only");
-    if (info->max_bits > 8192) return fail(BARK_ERR_ARG, "leaf-space path supports at most 8192 leaves per forest");
-    if (Bc > B) Bc = B;
-    if (Bc > 65535) Bc = 65535;
-    const bool want_minv = C > 0 || kinv_out != nullptr;
-    if (kinv_out && info->max_bits > 65535) return fail(BARK_ERR_ARG, "leaf-space inverse: too many leaves");
-    const LeafLayout g = make_leaf_layout(N, info->max_bits, m, Bc, C, kinv_out != nullptr, draws.S);
-    if (workspace_bytes < g.total) return fail(BARK_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, g.total);
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(BARK_ERR_ARG, "workspace must be 256-byte aligned");
-    if ((rc = set_lds_limits())) return rc;
-    hipStream_t caller = static_cast<hipStream_t>(stream_);
-    // the R x R sweep: N := R points, no leaf codes (A is filled by leafspace_prepare); posterior / inverse: R identity columns
-    // appended (M^-1 and w = M^-1 v)
-    const SweepShape sh = make_shape(g.L, g.R, 0);
-    if ((rc = ctx_events(ctx, (size_t)6 * sh.nrb + 6))) return rc;
-    Sweep sw(ctx, caller, g.L, workspace, sh, (int)m);
-    Mats &p = sw.p;
-    char *ws = static_cast<char *>(workspace);
-    uint32_t *codes = reinterpret_cast<uint32_t *>(ws + g.off_codes);
-    unsigned long long *planes = reinterpret_cast<unsigned long long *>(ws + g.off_planes);
-    double *yy = reinterpret_cast<double *>(ws + g.off_yy);
-    uint32_t *ccodes = reinterpret_cast<uint32_t *>(ws + g.off_ccodes);
-    double *Minv = reinterpret_cast<double *>(ws + g.off_minv);
-    double *wvec = reinterpret_cast<double *>(ws + g.off_w);
-    const bool use_scale = (flags & BARK_MLL_INCLUDE_SCALE) != 0;
-
-    if ((rc = leafspace_sumsq(y, (int)N, yy, caller))) return rc;
-    return sw.for_chunks(B, Bc, [&](int64_t c0, int64_t bc) -> int {
-        bark_pack_info sub = *info;
-        sub.B = bc;
-        const char *packed_c = static_cast<const char *>(packed) + (size_t)c0 * m * info->stride * 16;
-        rc = leafspace_factor_chunk(ctx, sw, sh, g, packed_c, &sub, X, N, d, y, yy, noise + c0, use_scale ? scale + c0 : nullptr,
-                                    want_minv, (flags & BARK_MLL_INCLUDE_2PI) ? 1 : 0, info_out + c0, mll_out ? mll_out + c0 : nullptr,
-                                    codes, planes, caller);
-        if (rc) return rc;
-        if (want_minv && sampling) {
-            // w = M^-1 v = V'z; then Wt = c w 1' + sqrt(scale/m) V' E' and the gather over the candidates' leaves (sample.hip)
-            const int R = (int)g.R, S = (int)draws.S;
-            if ((rc = launch_predict_reduce(p, R, R, (int)bc, nullptr, wvec, nullptr, g.L.splitk ? sw.slabs : nullptr, caller)))
-                return rc;
-            if ((rc = walk_one_hot(packed_c, &sub, cand, C, d, (int)g.W, ccodes, ctx->fault, caller))) return rc;
-            double *Wt = reinterpret_cast<double *>(ws + g.off_wt);
-            rc = sample_weights(p.A + (size_t)sh.nrb * NB, p.ld, p.bstride, wvec, draws.eps + (size_t)c0 * S * R, R, (int)g.Rpad, S,
-                                (int)g.Spad, noise + c0, scale + c0, (int)m, (int)bc, Wt, caller);
-            if (rc) return rc;
-            const bool full = draws.reduce == BARK_SAMPLE_FULL;
-            rc = sample_gather(ccodes, (int)g.W, (int)g.cpad, (int)C, Wt, (int)g.Rpad, (int)g.Spad, S, (int)m, (int)bc,
-                               draws.reduce, full ? draws.f_out + (size_t)c0 * S * C : nullptr,
-                               full ? nullptr : draws.red_out + (size_t)c0 * S, full ? nullptr : draws.idx_out + (size_t)c0 * S,
-                               reinterpret_cast<double *>(ws + g.off_part), reinterpret_cast<int64_t *>(ws + g.off_part_i),
-                               caller);
-            if (rc) return rc;
-        } else if (want_minv) {
-            const int R = (int)g.R;
-            if ((rc = leafspace_minv(sw, g, (int)bc, wvec, Minv, caller))) return rc;
-            if (C > 0) {
-                if ((rc = walk_one_hot(packed_c, &sub, cand, C, d, (int)g.W, ccodes, ctx->fault, caller))) return rc;
-                rc = leafspace_predict(ccodes, (int)g.W, (int)g.cpad, (int)C, wvec, Minv, R, noise + c0, scale + c0, (int)m,
-                                       (int)bc, mu_out + (size_t)c0 * C, var_out + (size_t)c0 * C, caller);
-                if (rc) return rc;
-            }
-            if (kinv_out) {
-                rc = leafspace_inverse(codes, (int)g.W, (int)g.npad, (int)N, Minv, wvec, R, y, noise + c0,
-                                       use_scale ? scale + c0 : nullptr, (int)m, (int)bc,
-                                       reinterpret_cast<double *>(ws + g.off_wm), kinv_out + (size_t)c0 * N * N,
-                                       kinv_y_out ? kinv_y_out + (size_t)c0 * N : nullptr, nullptr, caller);
-                if (rc) return rc;
-            }
-        }
-        hipLaunchKernelGGL(fault_info_kernel, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, caller, ctx->fault, p.info,
-                           (int)bc);
-        BARK_LAUNCH_CHECK();
-        return BARK_OK;
-    });
-}
-
-extern "C" {
 
 int bark_mll_leafspace_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d,
                            const double *y, const double *noise, const double *scale, int flags, const double *cand,
                            int64_t C, double *mll_out, double *mu_out, double *var_out, int32_t *info_out,
                            void *workspace, size_t workspace_bytes, int64_t Bc, void *stream_) {
-    return leafspace_run(ctx, packed, info, X, N, d, y, noise, scale, flags, cand, C, mll_out, mu_out, var_out, nullptr, nullptr,
-                         info_out, workspace, workspace_bytes, Bc, stream_);
+    error_buffer()[0] = 0;
+    if (!mll_out) return fail(BARK_ERR_ARG, "bark_mll_leafspace_hip: null argument");
+    if (C > 0 && (!cand || !mu_out || !var_out || !scale || !(flags & BARK_MLL_INCLUDE_SCALE)))
+        return fail(BARK_ERR_ARG, "leaf-space posterior needs cand, mu_out, var_out, scale and BARK_MLL_INCLUDE_SCALE");
+    if ((flags & BARK_MLL_INCLUDE_SCALE) && !scale) return fail(BARK_ERR_ARG, "BARK_MLL_INCLUDE_SCALE without scale");
+    if (flags & BARK_MLL_RHS_IDENTITY) return fail(BARK_ERR_ARG, "leaf-space path computes the MLL only");
+    LeafSystem sys;
+    int rc = sys.open("bark_mll_leafspace_hip", ctx, packed, info, X, N, d, y, noise, info_out, workspace, workspace_bytes, Bc, C,
+                      mll_needs(C), stream_);
+    if (rc) return rc;
+    const LeafAreas &a = sys.a;
+    const bool use_scale = (flags & BARK_MLL_INCLUDE_SCALE) != 0;
+    return sys.for_chunks([&](int64_t c0) -> int {
+        int r = sys.factor_chunk(noise + c0, use_scale ? scale + c0 : nullptr, info_out + c0, mll_out + c0,
+                                 (flags & BARK_MLL_INCLUDE_2PI) ? 1 : 0);
+        if (r) return r;
+        if (C > 0) {
+            if ((r = sys.solve_w_minv()) || (r = sys.walk_candidates(cand, C))) return r;
+            r = leafspace_predict(a.ccodes, sys.W, (int)a.cpad, (int)C, a.w, a.Minv, sys.R, noise + c0, scale + c0, sys.m, sys.bc,
+                                  mu_out + (size_t)c0 * C, var_out + (size_t)c0 * C, sys.caller);
+            if (r) return r;
+        }
+        return sys.close_chunk();
+    });
 }
 
 int bark_kernel_inverse_leafspace_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d,
                                       const double *y, const double *noise, const double *scale, int flags,
                                       double *mll_out, double *kinv_out, double *kinv_y_out, int32_t *info_out,
                                       void *workspace, size_t workspace_bytes, int64_t Bc, void *stream_) {
-    if (!kinv_out) {
-        error_buffer()[0] = 0;
-        return fail(BARK_ERR_ARG, "bark_kernel_inverse_leafspace_hip: kinv_out is null");
-    }
-    if (info && info->m > LEAF_INV_MAX_TREES) {  // before any launch: leaf_inverse_kernel's leaf lists must fit its LDS
-        error_buffer()[0] = 0;
+    error_buffer()[0] = 0;
+    if (!kinv_out) return fail(BARK_ERR_ARG, "bark_kernel_inverse_leafspace_hip: kinv_out is null");
+    if (info && info->m > LEAF_INV_MAX_TREES)  // leaf_inverse_kernel's leaf lists must fit its LDS
         return fail(BARK_ERR_ARG, "leaf-space inverse supports at most %d trees (got %lld)", LEAF_INV_MAX_TREES, (long long)info->m);
-    }
-    return leafspace_run(ctx, packed, info, X, N, d, y, noise, scale, flags, nullptr, 0, mll_out, nullptr, nullptr, kinv_out,
-                         kinv_y_out, info_out, workspace, workspace_bytes, Bc, stream_);
+    if (!mll_out) return fail(BARK_ERR_ARG, "bark_kernel_inverse_leafspace_hip: null argument");
+    if ((flags & BARK_MLL_INCLUDE_SCALE) && !scale) return fail(BARK_ERR_ARG, "BARK_MLL_INCLUDE_SCALE without scale");
+    if (flags & BARK_MLL_RHS_IDENTITY) return fail(BARK_ERR_ARG, "leaf-space path computes the MLL only");
+    LeafSystem sys;
+    int rc = sys.open("bark_kernel_inverse_leafspace_hip", ctx, packed, info, X, N, d, y, noise, info_out, workspace, workspace_bytes,
+                      Bc, 0, inverse_needs(), stream_);
+    if (rc) return rc;
+    const LeafAreas &a = sys.a;
+    const bool use_scale = (flags & BARK_MLL_INCLUDE_SCALE) != 0;
+    return sys.for_chunks([&](int64_t c0) -> int {
+        const double *scale_c = use_scale ? scale + c0 : nullptr;
+        int r = sys.factor_chunk(noise + c0, scale_c, info_out + c0, mll_out + c0, (flags & BARK_MLL_INCLUDE_2PI) ? 1 : 0);
+        if (r || (r = sys.solve_w_minv())) return r;
+        r = leafspace_inverse(a.codes, sys.W, (int)a.npad, (int)N, a.Minv, a.w, sys.R, y, noise + c0, scale_c, sys.m, sys.bc, a.Wm,
+                              kinv_out + (size_t)c0 * N * N, kinv_y_out ? kinv_y_out + (size_t)c0 * N : nullptr, nullptr, sys.caller);
+        if (r) return r;
+        return sys.close_chunk();
+    });
 }
 
+// Joint draws at the candidates: eps (B, S, R), and f_out (B, S, C) for BARK_SAMPLE_FULL or red_out / idx_out (B, S) for
+// BARK_SAMPLE_MAX / MIN.  No MLL.
 int bark_posterior_samples_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N,
                                int64_t d, const double *y, const double *noise, const double *scale, const double *cand,
                                int64_t C, const double *eps, int64_t S, int reduce, double *f_out, double *red_out,
@@ -1620,155 +1656,103 @@ int bark_posterior_samples_hip(bark_ctx *ctx, const void *packed, const bark_pac
     error_buffer()[0] = 0;
     if (reduce != BARK_SAMPLE_FULL && reduce != BARK_SAMPLE_MAX && reduce != BARK_SAMPLE_MIN)
         return fail(BARK_ERR_ARG, "bark_posterior_samples_hip: unknown reduce %d", reduce);
-    if (!info || !cand || !eps || !scale || (reduce == BARK_SAMPLE_FULL ? !f_out : (!red_out || !idx_out)))
+    const bool full = reduce == BARK_SAMPLE_FULL;
+    if (!info || !cand || !eps || !scale || (full ? !f_out : (!red_out || !idx_out)))
         return fail(BARK_ERR_ARG, "bark_posterior_samples_hip: null argument");
     if (C < 1 || S < 1 || S > (1 << 20))
         return fail(BARK_ERR_ARG, "bark_posterior_samples_hip: bad shape C=%lld S=%lld", (long long)C, (long long)S);
     if (info->m > 64) return fail(BARK_ERR_ARG, "leaf-space posterior samples support at most 64 trees (got %lld)", (long long)info->m);
-    LeafDraws draws;
-    draws.eps = eps;
-    draws.S = S;
-    draws.reduce = reduce;
-    draws.f_out = f_out;
-    draws.red_out = red_out;
-    draws.idx_out = idx_out;
-    return leafspace_run(ctx, packed, info, X, N, d, y, noise, scale, BARK_MLL_INCLUDE_SCALE, cand, C, nullptr, nullptr, nullptr,
-                         nullptr, nullptr, info_out, workspace, workspace_bytes, Bc, stream_, draws);
+    LeafSystem sys;
+    int rc = sys.open("bark_posterior_samples_hip", ctx, packed, info, X, N, d, y, noise, info_out, workspace, workspace_bytes, Bc, C,
+                      samples_needs(C, S), stream_);
+    if (rc) return rc;
+    const LeafAreas &a = sys.a;
+    return sys.for_chunks([&](int64_t c0) -> int {
+        int r = sys.factor_chunk(noise + c0, scale + c0, info_out + c0, nullptr, 0);
+        if (r || (r = sys.solve_w()) || (r = sys.walk_candidates(cand, C))) return r;
+        // Wt = c w 1' + sqrt(scale/m) V' E', then the gather over the candidates' leaves (sample.hip)
+        const Mats &p = sys.sw->p;
+        r = sample_weights(p.A + (size_t)sys.sh.nrb * NB, p.ld, p.bstride, a.w, eps + (size_t)c0 * S * sys.R, sys.R, (int)a.Rpad,
+                           (int)S, (int)a.Spad, noise + c0, scale + c0, sys.m, sys.bc, a.Wt, sys.caller);
+        if (r) return r;
+        r = sample_gather(a.ccodes, sys.W, (int)a.cpad, (int)C, a.Wt, (int)a.Rpad, (int)a.Spad, (int)S, sys.m, sys.bc, reduce,
+                          full ? f_out + (size_t)c0 * S * C : nullptr, full ? nullptr : red_out + (size_t)c0 * S,
+                          full ? nullptr : idx_out + (size_t)c0 * S, a.part, a.part_i, sys.caller);
+        if (r) return r;
+        return sys.close_chunk();
+    });
 }
 
-// Acquisition scan (include/bark_hip.h, kernels in acquire.hip): leafspace_run's posterior sequence per chunk of forests
-// (walk, I + c Z'Z, identity right-hand side, sweep, w, M^-1), consumed by acq_scan_kernel slab by slab of candidates before
-// the next chunk is prepared; the finish after the last chunk.
+// Acquisition scan (include/bark_hip.h, kernels in acquire.hip): w and M^-1 of a chunk of forests are consumed by
+// acq_scan_kernel slab by slab of candidates before the next chunk is prepared; the finish after the last chunk.
 int bark_acquisition_scan_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d,
                               const double *y, const double *noise, const double *scale, const double *cand, int64_t C,
                               double kappa, int kind, int variant, double *acq_out, double *best_out, int64_t *idx_out,
                               int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc, void *stream_) {
     error_buffer()[0] = 0;
-    int rc = check_ctx(ctx);
-    if (rc) return rc;
-    if (!packed || !info || !X || !y || !noise || !scale || !cand || !best_out || !idx_out || !info_out || !workspace)
-        return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: null argument");
-    const int64_t B = info->B, m = info->m;
-    if (N < 1 || d < 1 || B < 1 || Bc < 1 || C < 1 || N > (1 << 24) || C > (1 << 24))
-        return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: bad shape N=%lld d=%lld B=%lld Bc=%lld C=%lld", (long long)N,
-                    (long long)d, (long long)B, (long long)Bc, (long long)C);
+    if (!info || !scale || !cand || !best_out || !idx_out) return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: null argument");
+    if (C < 1) return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: bad shape C=%lld", (long long)C);
     if (kind != BARK_ACQ_LCB_MEAN && kind != BARK_ACQ_LCB_MIXTURE)
         return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: unknown kind %d", kind);
     if (!std::isfinite(kappa)) return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: kappa is not finite");
-    int var = 0;
-    if ((rc = bark_acquisition_plan(info->max_bits, m, variant, &var, nullptr))) return rc;
-    if (Bc > B) Bc = B;
-    if (Bc > 65535) Bc = 65535;
-    const AcqLayout a = make_acq_layout(N, info->max_bits, m, Bc, C);
-    const LeafLayout &g = a.g;
-    if (workspace_bytes < a.total) return fail(BARK_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, a.total);
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(BARK_ERR_ARG, "workspace must be 256-byte aligned");
-    if ((rc = set_lds_limits())) return rc;
-    hipStream_t caller = static_cast<hipStream_t>(stream_);
-    const SweepShape sh = make_shape(g.L, g.R, 0);
-    if ((rc = ctx_events(ctx, (size_t)6 * sh.nrb + 6))) return rc;
-    Sweep sw(ctx, caller, g.L, workspace, sh, (int)m);
-    char *ws = static_cast<char *>(workspace);
-    uint32_t *codes = reinterpret_cast<uint32_t *>(ws + g.off_codes);
-    unsigned long long *planes = reinterpret_cast<unsigned long long *>(ws + g.off_planes);
-    double *yy = reinterpret_cast<double *>(ws + g.off_yy);
-    uint32_t *ccodes = reinterpret_cast<uint32_t *>(ws + g.off_ccodes);
-    double *Minv = reinterpret_cast<double *>(ws + g.off_minv);
-    double *wvec = reinterpret_cast<double *>(ws + g.off_w);
-    double *tab = reinterpret_cast<double *>(ws + a.off_tab);
-    double *acc = reinterpret_cast<double *>(ws + a.off_acc);
-    const int R = (int)g.R;
-
-    if ((rc = leafspace_sumsq(y, (int)N, yy, caller))) return rc;
-    rc = sw.for_chunks(B, Bc, [&](int64_t c0, int64_t bc) -> int {
-        bark_pack_info sub = *info;
-        sub.B = bc;
-        const char *packed_c = static_cast<const char *>(packed) + (size_t)c0 * m * info->stride * 16;
-        int r = leafspace_factor_chunk(ctx, sw, sh, g, packed_c, &sub, X, N, d, y, yy, noise + c0, scale + c0, true, 0, info_out + c0,
-                                       nullptr, codes, planes, caller);
-        if (r) return r;
-        if ((r = leafspace_minv(sw, g, (int)bc, wvec, Minv, caller))) return r;
-        if (var == 1 && (r = acq_pack(Minv, wvec, R, (int)bc, tab, caller))) return r;
-        for (int64_t s0 = 0; s0 < C; s0 += a.slab) {
-            const int64_t n = C - s0 < a.slab ? C - s0 : a.slab;
-            if ((r = walk_one_hot(packed_c, &sub, cand + (size_t)s0 * d, n, d, (int)g.W, ccodes, ctx->fault, caller))) return r;
-            r = acq_scan(var, ccodes, (int)g.W, (int)bark_leaf_npad(n), (int)n, wvec, Minv, tab, R, noise + c0, scale + c0, (int)m,
-                         (int)bc, kappa, c0 == 0, acc + s0, (size_t)C, caller);
+    int var = 0, rc;
+    if ((rc = bark_acquisition_plan(info->max_bits, info->m, variant, &var, nullptr))) return rc;
+    LeafSystem sys;
+    rc = sys.open("bark_acquisition_scan_hip", ctx, packed, info, X, N, d, y, noise, info_out, workspace, workspace_bytes, Bc, C,
+                  scan_needs(C), stream_);
+    if (rc) return rc;
+    const LeafAreas &a = sys.a;
+    rc = sys.for_chunks([&](int64_t c0) -> int {
+        int r = sys.factor_chunk(noise + c0, scale + c0, info_out + c0, nullptr, 0);
+        if (r || (r = sys.solve_w_minv())) return r;
+        if (var == 1 && (r = acq_pack(a.Minv, a.w, sys.R, sys.bc, a.tab, sys.caller))) return r;
+        for (int64_t s0 = 0; s0 < C; s0 += ACQ_SLAB) {
+            const int64_t n = C - s0 < ACQ_SLAB ? C - s0 : ACQ_SLAB;
+            if ((r = sys.walk_candidates(cand + (size_t)s0 * d, n))) return r;
+            r = acq_scan(var, a.ccodes, sys.W, (int)bark_leaf_npad(n), (int)n, a.w, a.Minv, a.tab, sys.R, noise + c0, scale + c0, sys.m,
+                         sys.bc, kappa, c0 == 0, a.acc + s0, (size_t)C, sys.caller);
             if (r) return r;
         }
-        hipLaunchKernelGGL(fault_info_kernel, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, caller, ctx->fault, sw.p.info,
-                           (int)bc);
-        BARK_LAUNCH_CHECK();
-        return BARK_OK;
+        return sys.close_chunk();
     });
     if (rc) return rc;
-    return acq_finish(acc, C, (int)B, kappa, kind, acq_out, reinterpret_cast<double *>(ws + a.off_part),
-                      reinterpret_cast<int64_t *>(ws + a.off_part_i), info_out, best_out, idx_out, caller);
+    return acq_finish(a.acc, C, (int)sys.B, kappa, kind, acq_out, a.part, a.part_i, info_out, best_out, idx_out, sys.caller);
 }
 
-// The noise/scale half of the sampler step for nc chains (include/bark_hip.h): leafspace_run's MLL + inverse sequence for one
-// chunk of nc forests (the same helpers), with the Metropolis decision between the MLL and the N x N expansion, which only
-// accepted chains run.
+// The noise/scale half of the sampler step for nc chains (include/bark_hip.h): the MLL + inverse sequence for one chunk of nc
+// forests, with the Metropolis decision between the MLL and the N x N expansion, which only accepted chains run.  The
+// decision reads the fault flag itself, so the chunk is not closed.
 int bark_noise_scale_step_chains_hip(bark_ctx *ctx, double *K_inv, int64_t N, int64_t nc, const void *packed,
                                      const bark_pack_info *info, const double *X, int64_t d, const double *y,
                                      const double *new_noise, const double *new_scale, const double *log_q_prior,
                                      const double *log_u, double *state, int32_t *accept_out, void *workspace,
                                      size_t workspace_bytes, void *stream_) {
     error_buffer()[0] = 0;
-    int rc = check_ctx(ctx);
-    if (rc) return rc;
-    if (!K_inv || !packed || !info || !X || !y || !new_noise || !new_scale || !log_q_prior || !log_u || !state || !accept_out ||
-        !workspace)
+    if (!K_inv || !info || !new_scale || !log_q_prior || !log_u || !state)
         return fail(BARK_ERR_ARG, "bark_noise_scale_step_chains_hip: null argument");
     if (nc < 1 || nc > 64) return fail(BARK_ERR_ARG, "bark_noise_scale_step_chains_hip: 1 to 64 chains (got %lld)", (long long)nc);
     if (info->B != nc)
         return fail(BARK_ERR_ARG, "bark_noise_scale_step_chains_hip: %lld packed forests for %lld chains", (long long)info->B,
                     (long long)nc);
-    const int64_t m = info->m;
-    if (N < 1 || d < 1 || N > (1 << 24) || m < 1)
-        return fail(BARK_ERR_ARG, "bark_noise_scale_step_chains_hip: bad shape N=%lld d=%lld m=%lld", (long long)N, (long long)d,
-                    (long long)m);
-    if (m > LEAF_INV_MAX_TREES)
-        return fail(BARK_ERR_ARG, "bark_noise_scale_step_chains_hip: at most %d trees (got %lld)", LEAF_INV_MAX_TREES, (long long)m);
-    if (info->max_bits < 1 || info->max_bits > 8192)
-        return fail(BARK_ERR_ARG, "bark_noise_scale_step_chains_hip: at most 8192 leaves per forest (got %lld)", (long long)info->max_bits);
-    const LeafLayout g = make_leaf_layout(N, info->max_bits, m, nc, 0, true);
-    const size_t need = bark_noise_scale_step_chains_workspace_bytes(N, info->max_bits, m, nc);
-    if (workspace_bytes < need) return fail(BARK_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, need);
-    if (reinterpret_cast<uintptr_t>(workspace) & 255) return fail(BARK_ERR_ARG, "workspace must be 256-byte aligned");
-    if ((rc = set_lds_limits())) return rc;
-    hipStream_t caller = static_cast<hipStream_t>(stream_);
-    const SweepShape sh = make_shape(g.L, g.R, 0);
-    if ((rc = ctx_events(ctx, (size_t)6 * sh.nrb + 6))) return rc;
-    Sweep sw(ctx, caller, g.L, workspace, sh, (int)m);
-    char *ws = static_cast<char *>(workspace);
-    uint32_t *codes = reinterpret_cast<uint32_t *>(ws + g.off_codes);
-    unsigned long long *planes = reinterpret_cast<unsigned long long *>(ws + g.off_planes);
-    double *yy = reinterpret_cast<double *>(ws + g.off_yy);
-    double *Minv = reinterpret_cast<double *>(ws + g.off_minv);
-    double *wvec = reinterpret_cast<double *>(ws + g.off_w);
-    double *Wm = reinterpret_cast<double *>(ws + g.off_wm);
-    size_t o = g.total;
-    double *new_mll = reinterpret_cast<double *>(ws + o);
-    o = align256(o + (size_t)nc * sizeof(double));
-    int32_t *sweep_info = reinterpret_cast<int32_t *>(ws + o);
-    o = align256(o + (size_t)nc * sizeof(int32_t));
-    double *kinv_y = reinterpret_cast<double *>(ws + o);
-    const int R = (int)g.R, bc = (int)nc;
-
-    if ((rc = leafspace_sumsq(y, (int)N, yy, caller))) return rc;
-    return sw.for_chunks(nc, nc, [&](int64_t, int64_t) -> int {
-        rc = leafspace_factor_chunk(ctx, sw, sh, g, packed, info, X, N, d, y, yy, new_noise, new_scale, true, 0, sweep_info, new_mll,
-                                    codes, planes, caller);
-        if (rc) return rc;
-        rc = noise_scale_decide(new_mll, state, new_noise, log_q_prior, log_u, sweep_info, ctx->fault, bc, accept_out, caller);
-        if (rc) return rc;
+    if (info->m > LEAF_INV_MAX_TREES)
+        return fail(BARK_ERR_ARG, "bark_noise_scale_step_chains_hip: at most %d trees (got %lld)", LEAF_INV_MAX_TREES,
+                    (long long)info->m);
+    LeafSystem sys;
+    int rc = sys.open("bark_noise_scale_step_chains_hip", ctx, packed, info, X, N, d, y, new_noise, accept_out, workspace,
+                      workspace_bytes, nc, 0, chain_step_needs(), stream_);
+    if (rc) return rc;
+    const LeafAreas &a = sys.a;
+    return sys.for_chunks([&](int64_t) -> int {
+        const int bc = sys.bc;
+        int r = sys.factor_chunk(new_noise, new_scale, a.sweep_info, a.new_mll, 0);
+        if (r) return r;
+        r = noise_scale_decide(a.new_mll, state, new_noise, log_q_prior, log_u, a.sweep_info, ctx->fault, bc, accept_out, sys.caller);
         // w and M^-1 for every chain (R x R); the N x R and N x N passes run for accepted chains only
-        if ((rc = leafspace_minv(sw, g, bc, wvec, Minv, caller))) return rc;
-        rc = leafspace_inverse(codes, (int)g.W, (int)g.npad, (int)N, Minv, wvec, R, y, new_noise, new_scale, (int)m, bc, Wm, K_inv,
-                               kinv_y, accept_out, caller);
-        if (rc) return rc;
-        return noise_scale_state(kinv_y, y, (int)N, new_mll, accept_out, bc, state, caller);
+        if (r || (r = sys.solve_w_minv())) return r;
+        r = leafspace_inverse(a.codes, sys.W, (int)a.npad, (int)N, a.Minv, a.w, sys.R, y, new_noise, new_scale, sys.m, bc, a.Wm, K_inv,
+                              a.kinv_y, accept_out, sys.caller);
+        if (r) return r;
+        return noise_scale_state(a.kinv_y, y, (int)N, a.new_mll, accept_out, bc, state, sys.caller);
     });
 }
 

@@ -13,6 +13,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from typing import NamedTuple
 
 import numpy as np
 
@@ -37,21 +38,28 @@ def _feat_types_of(domain_or_feat_types):
         raise TypeError("pass feat_types (int array: 0=Cat, 1=Int, 2=Cont) or a bofire Domain") from exc
 
 
-def _fit_chunk(B: int, need, budget_bytes: int | None = None) -> int:
-    """Largest chunk of forests whose workspace `need(chunk)` (monotone) fits the HBM budget: default 70 % of the
-    free device memory (counting the cached workspace as free), or $BARK_WORKSPACE_GB."""
+def _hbm_budget(nbytes: int) -> int | None:
+    """The HBM budget a request of `nbytes` is held against: $BARK_WORKSPACE_GB, else 70 % of the free device memory
+    (counting this thread's cached scratch as free).  None — no limit, and the driver is not asked (a latency-sensitive
+    caller may be in a sampler loop) — for a request of at most 256 MiB without $BARK_WORKSPACE_GB."""
     import torch
 
-    if budget_bytes is None and not os.environ.get("BARK_WORKSPACE_GB") and need(B) <= (256 << 20):
-        return int(B)  # small enough not to ask the driver (a latency-sensitive caller may be in a sampler loop);
-        # an explicit budget (argument or $BARK_WORKSPACE_GB) is always honoured
+    env = os.environ.get("BARK_WORKSPACE_GB")
+    if env:
+        return int(float(env) * (1 << 30))
+    if nbytes <= (256 << 20):
+        return None
+    free, _total = torch.cuda.mem_get_info()
+    return int(0.7 * (free + _lib.workspace_bytes()))
+
+
+def _fit_chunk(B: int, need, budget_bytes: int | None = None) -> int:
+    """Largest chunk of forests whose workspace `need(chunk)` (monotone) fits the HBM budget: `_hbm_budget`, or the
+    explicit `budget_bytes`, which is always honoured."""
     if budget_bytes is None:
-        env = os.environ.get("BARK_WORKSPACE_GB")
-        if env:
-            budget_bytes = int(float(env) * (1 << 30))
-        else:
-            free, _total = torch.cuda.mem_get_info()
-            budget_bytes = int(0.7 * (free + _lib.workspace_bytes()))  # this thread's scratch counts as free
+        budget_bytes = _hbm_budget(need(B))
+        if budget_bytes is None:
+            return int(B)
     if need(B) <= budget_bytes:
         return int(B)
     lo, hi = 1, int(B)
@@ -70,34 +78,45 @@ def choose_chunk(B: int, N: int, C: int, m: int, budget_bytes: int | None = None
     return _fit_chunk(B, lambda k: int(lib.bark_mll_workspace_bytes(N, C, m, k)), budget_bytes)
 
 
+def _forest3(forest):
+    """The forest samples with their leading dims (chains, samples) flattened: (B, m, nodes) records."""
+    nodes = _as_nodes(forest, 2)
+    return nodes.reshape(-1, *nodes.shape[-2:])
+
+
+def _y_vector(y, N: int):
+    """y as a contiguous float64 device vector of N entries."""
+    import torch
+
+    yd = _lib.to_device(y.detach() if _is_torch(y) else np.asarray(y, dtype=np.float64))
+    yd = yd.to(torch.float64).reshape(-1).contiguous()
+    if yd.shape[0] != N:
+        raise ValueError(f"y has {yd.shape[0]} rows, X has {N}")
+    return yd
+
+
+def _forest_vector(v):
+    """A per-forest parameter (noise, scale, shift) as a contiguous float64 host vector."""
+    return np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
+
+
 def _run(forest, noise, scale, X, y, feat_types, flags, cand=None, timing=None, chunk=None, shift=None,
          want_cov=False):
     import torch
 
     lib = _lib.lib()
     ft = _feat_types(feat_types)
-    nodes = _as_nodes(forest, 2)
-    nodes3 = nodes.reshape(-1, *nodes.shape[-2:])
+    nodes3 = _forest3(forest)
     B = nodes3.shape[0]
     Xd, _ = _points(X, ft.shape[0])
     N, d = Xd.shape
-    yd = _lib.to_device(y.detach() if _is_torch(y) else np.asarray(y, dtype=np.float64))
-    yd = yd.to(torch.float64).reshape(-1).contiguous()
-    if yd.shape[0] != N:
-        raise ValueError(f"y has {yd.shape[0]} rows, X has {N}")
-    noise_d = _lib.to_device(np.ascontiguousarray(np.asarray(noise, dtype=np.float64).reshape(-1)))
-    if noise_d.shape[0] != B:
-        raise ValueError(f"noise has {noise_d.shape[0]} entries for {B} forests")
-    scale_d = None
-    if scale is not None:
-        scale_d = _lib.to_device(np.ascontiguousarray(np.asarray(scale, dtype=np.float64).reshape(-1)))
-        if scale_d.shape[0] != B:
-            raise ValueError(f"scale has {scale_d.shape[0]} entries for {B} forests")
-    shift_d = None
-    if shift is not None:
-        shift_d = _lib.to_device(np.ascontiguousarray(np.asarray(shift, dtype=np.float64).reshape(-1)))
-        if shift_d.shape[0] != B:
-            raise ValueError(f"shift has {shift_d.shape[0]} entries for {B} forests")
+    yd = _y_vector(y, N)
+    per_forest = {}
+    for name, v in (("noise", noise), ("scale", scale), ("shift", shift)):
+        per_forest[name] = None if v is None else _lib.to_device(_forest_vector(v))
+        if v is not None and per_forest[name].shape[0] != B:
+            raise ValueError(f"{name} has {per_forest[name].shape[0]} entries for {B} forests")
+    noise_d, scale_d, shift_d = per_forest["noise"], per_forest["scale"], per_forest["shift"]
     C = 0
     cand_d = mu = var = cov = None
     if flags & _lib.MLL_RHS_IDENTITY:
@@ -181,8 +200,7 @@ def batched_kernel_inverse(forest, noise, scale, X, y, feat_types, *, no_null: b
     method="leafspace" (no_null=False only) builds the same three results from the R x R leaf-space system,
     K_inv = (I - c Z M^-1 Z') / sigma2 (include/bark_hip.h) — what a single chain's noise/scale step wants,
     where one N x N factorisation cannot fill the GPU."""
-    nodes = _as_nodes(forest, 2)
-    nodes3 = nodes.reshape(-1, *nodes.shape[-2:])
+    nodes3 = _forest3(forest)
     scale = np.asarray(scale, dtype=np.float64).reshape(-1)
     if method == "leafspace":
         if no_null:
@@ -208,9 +226,8 @@ def _inverse_results(mll_noconst, K_inv_y, K_inv, X, y, return_device):
     """mll = 0.5(-y'K^-1 y - logdet)  =>  logdet = -2 mll - y'K^-1 y."""
     import torch
 
-    yd = _lib.to_device(y.detach() if _is_torch(y) else np.asarray(y, dtype=np.float64)).to(torch.float64).reshape(-1)
-    yd = yd.contiguous()
     B, N = K_inv_y.shape
+    yd = _y_vector(y, N)
     logdet = torch.empty(B, dtype=torch.float64, device=K_inv_y.device)  # -(y' K^-1 y) - 2 mll per forest sample
     _lib.check(_lib.lib().bark_rowdot_hip(_lib.ptr(K_inv_y), B, N, N, _lib.ptr(yd), -1.0, _lib.ptr(mll_noconst.contiguous()),
                                           -2.0, _lib.ptr(logdet), _lib.stream_ptr()))
@@ -219,62 +236,85 @@ def _inverse_results(mll_noconst, K_inv_y, K_inv, X, y, return_device):
     return K_inv.cpu().numpy(), K_inv_y.cpu().numpy(), logdet.cpu().numpy()
 
 
+class LeafInputs(NamedTuple):
+    """What every leaf-space entry point takes, validated and on the device (`_leaf_inputs`)."""
+
+    nodes3: np.ndarray
+    ft: np.ndarray
+    pf: object  # PackedForest
+    Xd: object
+    yd: object
+    noise_d: object
+    scale_d: object  # None: no scale
+    cand_d: object  # None: no candidates
+    B: int
+    m: int
+    N: int
+    d: int
+    C: int
+    R: int  # max_bits of the packed forests: the width of the leaf-space system
+    device: object
+
+
+def _leaf_inputs(forest, noise, scale, X, y, feat_types, cand=None) -> LeafInputs:
+    """The inputs of a leaf-space call.  The checks that need no device come first; without a GPU the first device
+    tensor raises RuntimeError (no CPU fallback)."""
+    nodes3 = _forest3(forest)
+    ft = _feat_types(feat_types)
+    B, m = int(nodes3.shape[0]), int(nodes3.shape[1])
+    noise = _forest_vector(noise)
+    scale = None if scale is None else _forest_vector(scale)
+    if noise.shape[0] != B or (scale is not None and scale.shape[0] != B):
+        raise ValueError(f"noise/scale must have one entry per forest ({B})")
+    Xd, _ = _points(X, ft.shape[0])
+    N, d = Xd.shape
+    yd = _y_vector(y, N)
+    cand_d = None if cand is None else _points(cand, ft.shape[0])[0]
+    pf = packed_forest(nodes3, ft)
+    return LeafInputs(nodes3, ft, pf, Xd, yd, _lib.to_device(noise), None if scale is None else _lib.to_device(scale), cand_d,
+                      B, m, int(N), int(d), 0 if cand_d is None else int(cand_d.shape[0]), int(pf.info.max_bits), Xd.device)
+
+
+def _leaf_call(q: LeafInputs, fn, need, chunk, *args, fit_B=None):
+    """Run the leaf-space entry point `fn` on the inputs q: the chunk of forests that fits the budget (`need(k)`: the
+    entry point's workspace bytes at k resident forests; fit_B caps the search), the workspace, the call and its status.
+    args: what the entry point takes between `scale` and `info_out`."""
+    import torch
+
+    info = torch.empty(q.B, dtype=torch.int32, device=q.device)
+    Bc = int(chunk) if chunk else _fit_chunk(fit_B or q.B, need)
+    ws = _lib.workspace(need(Bc))
+    _lib.check(fn(_lib.ctx(), _lib.ptr(q.pf.packed), q.pf.info_ref, _lib.ptr(q.Xd), q.N, q.d, _lib.ptr(q.yd), _lib.ptr(q.noise_d),
+                  _lib.ptr(q.scale_d), *args, _lib.ptr(info), _lib.ptr(ws), ws.numel(), Bc, _lib.stream_ptr()))
+    _raise_on_info(info, "leaf-space system")
+
+
 def _run_leafspace(forest, noise, scale, X, y, feat_types, flags, chunk=None, cand=None, want_inverse=False):
     """Leaf-space evaluation (bark_mll_leafspace_hip): R x R system instead of N x N.
     Returns the (B,) MLL tensor, (mll, mu, var) when candidates are given, or (mll, K_inv_y, K_inv) with
     `want_inverse` (bark_kernel_inverse_leafspace_hip)."""
     import torch
 
+    if want_inverse and cand is not None:
+        raise ValueError("candidates and want_inverse are separate calls")
     lib = _lib.lib()
-    ft = _feat_types(feat_types)
-    nodes = _as_nodes(forest, 2)
-    nodes3 = nodes.reshape(-1, *nodes.shape[-2:])
-    B = nodes3.shape[0]
-    Xd, _ = _points(X, ft.shape[0])
-    N, d = Xd.shape
-    yd = _lib.to_device(y.detach() if _is_torch(y) else np.asarray(y, dtype=np.float64))
-    yd = yd.to(torch.float64).reshape(-1).contiguous()
-    if yd.shape[0] != N:
-        raise ValueError(f"y has {yd.shape[0]} rows, X has {N}")
-    noise_d = _lib.to_device(np.ascontiguousarray(np.asarray(noise, dtype=np.float64).reshape(-1)))
-    scale_d = None if scale is None else _lib.to_device(np.ascontiguousarray(np.asarray(scale, dtype=np.float64).reshape(-1)))
-    if noise_d.shape[0] != B or (scale_d is not None and scale_d.shape[0] != B):
-        raise ValueError(f"noise/scale must have one entry per forest ({B})")
-    C = 0
-    cand_d = mu = var = None
-    if cand is not None:
-        cand_d, _ = _points(cand, ft.shape[0])
-        C = cand_d.shape[0]
-        mu = torch.empty((B, C), dtype=torch.float64, device=Xd.device)
-        var = torch.empty((B, C), dtype=torch.float64, device=Xd.device)
-    pf = packed_forest(nodes3, ft)
-    R = int(pf.info.max_bits)
-    out = torch.empty(B, dtype=torch.float64, device=Xd.device)
-    info = torch.empty(B, dtype=torch.int32, device=Xd.device)
-    K_inv = K_inv_y = None
+    q = _leaf_inputs(forest, noise, scale, X, y, feat_types, cand)
+    B, N, C, R, m = q.B, q.N, q.C, q.R, q.pf.m
+
+    def empty(*shape):
+        return torch.empty(shape, dtype=torch.float64, device=q.device)
+
+    out = empty(B)
     if want_inverse:
-        if cand is not None:
-            raise ValueError("candidates and want_inverse are separate calls")
-        K_inv = torch.empty((B, N, N), dtype=torch.float64, device=Xd.device)
-        K_inv_y = torch.empty((B, N), dtype=torch.float64, device=Xd.device)
-        Bc = int(chunk) if chunk else _fit_chunk(
-            min(B, max(1, (1 << 30) // max(1, 8 * N * R))),  # keep the (Bc, N, R) row-sum scratch modest
-            lambda k: int(lib.bark_kernel_inverse_leafspace_workspace_bytes(N, R, pf.m, k)))
-        ws = _lib.workspace(int(lib.bark_kernel_inverse_leafspace_workspace_bytes(N, R, pf.m, Bc)))
-        _lib.check(lib.bark_kernel_inverse_leafspace_hip(_lib.ctx(), _lib.ptr(pf.packed), pf.info_ref, _lib.ptr(Xd), N, d, _lib.ptr(yd),
-                                                         _lib.ptr(noise_d), _lib.ptr(scale_d), flags, _lib.ptr(out),
-                                                         _lib.ptr(K_inv), _lib.ptr(K_inv_y), _lib.ptr(info), _lib.ptr(ws),
-                                                         ws.numel(), Bc, _lib.stream_ptr()))
-    else:
-        Bc = int(chunk) if chunk else _fit_chunk(B, lambda k: int(lib.bark_mll_leafspace_workspace_bytes(N, R, pf.m, k, C)))
-        ws = _lib.workspace(int(lib.bark_mll_leafspace_workspace_bytes(N, R, pf.m, Bc, C)))
-        _lib.check(lib.bark_mll_leafspace_hip(_lib.ctx(), _lib.ptr(pf.packed), pf.info_ref, _lib.ptr(Xd), N, d, _lib.ptr(yd),
-                                              _lib.ptr(noise_d), _lib.ptr(scale_d), flags, _lib.ptr(cand_d), C,
-                                              _lib.ptr(out), _lib.ptr(mu), _lib.ptr(var), _lib.ptr(info),
-                                              _lib.ptr(ws), ws.numel(), Bc, _lib.stream_ptr()))
-    _raise_on_info(info, "leaf-space system")
-    if want_inverse:
+        K_inv, K_inv_y = empty(B, N, N), empty(B, N)
+        _leaf_call(q, lib.bark_kernel_inverse_leafspace_hip,
+                   lambda k: int(lib.bark_kernel_inverse_leafspace_workspace_bytes(N, R, m, k)), chunk,
+                   flags, _lib.ptr(out), _lib.ptr(K_inv), _lib.ptr(K_inv_y),
+                   fit_B=min(B, max(1, (1 << 30) // max(1, 8 * N * R))))  # keep the (Bc, N, R) row-sum scratch modest
         return out, K_inv_y, K_inv
+    mu, var = (empty(B, C), empty(B, C)) if C else (None, None)
+    _leaf_call(q, lib.bark_mll_leafspace_hip, lambda k: int(lib.bark_mll_leafspace_workspace_bytes(N, R, m, k, C)), chunk,
+               flags, _lib.ptr(q.cand_d), C, _lib.ptr(out), _lib.ptr(mu), _lib.ptr(var))
     return out if cand is None else (out, mu, var)
 
 

@@ -20,8 +20,8 @@ import math
 import numpy as np
 
 from .. import _lib
-from ..fitting.mll import _feat_types_of, _fit_chunk, _raise_on_info
-from ..forest import _as_nodes, _feat_types, _is_torch, _points, packed_forest
+from ..fitting.mll import _feat_types_of, _forest3, _leaf_call, _leaf_inputs
+from ..forest import _is_torch
 
 KINDS = {"lcb_mean": _lib.ACQ_LCB_MEAN, "lcb_mixture": _lib.ACQ_LCB_MIXTURE}
 VARIANTS = {"auto": 0, "lds": 1, "global": 2}
@@ -68,50 +68,26 @@ def acquisition_scan(model, data, candidates, domain, kappa: float = 1.96, kind:
         raise ValueError(f"kappa must be finite, got {kappa}")
     forest, noise, scale = model
     train_x, train_y = data
-    nodes = _as_nodes(forest, 2)
-    nodes3 = nodes.reshape(-1, *nodes.shape[-2:])
-    ft = _feat_types(_feat_types_of(domain))
-    B, m = int(nodes3.shape[0]), int(nodes3.shape[1])
+    nodes3 = _forest3(forest)
+    m = int(nodes3.shape[1])
     if m > MAX_TREES:
         raise ValueError(f"acquisition scan supports at most {MAX_TREES} trees (got {m})")
-    noise = np.ascontiguousarray(np.asarray(noise, dtype=np.float64).reshape(-1))
-    scale = np.ascontiguousarray(np.asarray(scale, dtype=np.float64).reshape(-1))
-    if noise.shape[0] != B or scale.shape[0] != B:
-        raise ValueError(f"noise/scale must have one entry per forest ({B})")
     if len(candidates) < 1:
         raise ValueError("acquisition scan needs at least one candidate")
 
     import torch
 
-    lib = _lib.lib()
-    _lib.torch_device()  # RuntimeError without a GPU: no CPU fallback
-    Xd, _ = _points(train_x, ft.shape[0])
-    N, d = Xd.shape
-    dev = Xd.device
-    yd = _lib.to_device(train_y.detach() if _is_torch(train_y) else np.asarray(train_y, dtype=np.float64))
-    yd = yd.to(torch.float64).reshape(-1).contiguous()
-    if yd.shape[0] != N:
-        raise ValueError(f"y has {yd.shape[0]} rows, X has {N}")
-    cand_d, _ = _points(candidates, ft.shape[0])
-    C = int(cand_d.shape[0])
-    pf = packed_forest(nodes3, ft)
-    R = int(pf.info.max_bits)
+    q = _leaf_inputs(nodes3, noise, scale, train_x, train_y, _feat_types_of(domain), candidates)
+    C, R, dev = q.C, q.R, q.device
     if R > MAX_LEAVES:
         raise ValueError(f"acquisition scan supports at most {MAX_LEAVES} leaves per forest (got {R})")
     acquisition_plan(R, m, variant)  # refuses variant="lds" past the LDS limit before anything is allocated
-    noise_d, scale_d = _lib.to_device(noise), _lib.to_device(scale)
     acq = torch.empty(C, dtype=torch.float64, device=dev) if return_values else None
     best = torch.empty((), dtype=torch.float64, device=dev)
     idx = torch.empty((), dtype=torch.int64, device=dev)
-    info = torch.empty(B, dtype=torch.int32, device=dev)
-    need = lambda k: int(lib.bark_acquisition_scan_workspace_bytes(N, R, pf.m, k, C))  # noqa: E731
-    Bc = int(chunk) if chunk else _fit_chunk(B, need)
-    ws = _lib.workspace(need(Bc))
-    _lib.check(lib.bark_acquisition_scan_hip(_lib.ctx(), _lib.ptr(pf.packed), pf.info_ref, _lib.ptr(Xd), N, d, _lib.ptr(yd),
-                                             _lib.ptr(noise_d), _lib.ptr(scale_d), _lib.ptr(cand_d), C, kappa, KINDS[kind],
-                                             VARIANTS[variant], _lib.ptr(acq), _lib.ptr(best), _lib.ptr(idx), _lib.ptr(info),
-                                             _lib.ptr(ws), ws.numel(), Bc, _lib.stream_ptr()))
-    _raise_on_info(info, "leaf-space system")
+    lib = _lib.lib()
+    _leaf_call(q, lib.bark_acquisition_scan_hip, lambda k: int(lib.bark_acquisition_scan_workspace_bytes(q.N, R, q.pf.m, k, C)),
+               chunk, _lib.ptr(q.cand_d), C, kappa, KINDS[kind], VARIANTS[variant], _lib.ptr(acq), _lib.ptr(best), _lib.ptr(idx))
     if _is_torch(candidates):
         return (best, idx, acq) if return_values else (best, idx)
     out = (float(best.item()), int(idx.item()))

@@ -16,14 +16,13 @@ no longer exists; `bark_amd.optimizer.thompson_sampling` builds on this one.
 from __future__ import annotations
 
 import ctypes
-import os
 from typing import NamedTuple
 
 import numpy as np
 
 from .. import _lib
-from ..fitting.mll import _feat_types_of, _fit_chunk, _raise_on_info, _run, _run_leafspace
-from ..forest import _as_nodes, _feat_types, _is_torch, _points, packed_forest
+from ..fitting.mll import _feat_types_of, _forest3, _hbm_budget, _leaf_call, _leaf_inputs, _run, _run_leafspace
+from ..forest import _feat_types, _is_torch
 
 
 class BARKModel(NamedTuple):
@@ -88,11 +87,6 @@ _REDUCE = {None: _lib.SAMPLE_FULL, "max": _lib.SAMPLE_MAX, "min": _lib.SAMPLE_MI
 MAX_SAMPLE_TREES, MAX_SAMPLE_LEAVES = 64, 8192  # limits of the leaf-space posterior (include/bark_hip.h)
 
 
-def _forest3(forest):
-    nodes = _as_nodes(forest, 2)
-    return nodes.reshape(-1, *nodes.shape[-2:])
-
-
 def posterior_sample_dim(forest, domain) -> int:
     """R, the width of the draws' `eps` (B, S, R): max_bits of the packed forest samples (the one-hot leaf-code width).
     Host-side packer query; no GPU needed."""
@@ -105,19 +99,10 @@ def posterior_sample_dim(forest, domain) -> int:
 
 
 def _check_output_budget(nbytes: int, what: str):
-    """Refuse outputs larger than the HBM budget `_fit_chunk` works with (70 % of the free device memory, or
-    $BARK_WORKSPACE_GB): unlike the workspace they cannot be chunked."""
-    import torch
-
-    env = os.environ.get("BARK_WORKSPACE_GB")
-    if not env and nbytes <= (256 << 20):
-        return
-    if env:
-        budget = int(float(env) * (1 << 30))
-    else:
-        free, _total = torch.cuda.mem_get_info()
-        budget = int(0.7 * (free + _lib.workspace_bytes()))
-    if nbytes > budget:
+    """Refuse outputs larger than the HBM budget `_fit_chunk` works with (`_hbm_budget`): unlike the workspace they
+    cannot be chunked."""
+    budget = _hbm_budget(nbytes)
+    if budget is not None and nbytes > budget:
         raise ValueError(f"{what} needs {nbytes / 2**30:.2f} GiB, more than the {budget / 2**30:.2f} GiB budget: "
                          "use reduce='max' / reduce='min' or fewer draws")
 
@@ -145,29 +130,14 @@ def posterior_samples(model, data, candidates, domain, num_samples, *, generator
     forest, noise, scale = model
     train_x, train_y = data
     nodes3 = _forest3(forest)
-    ft = _feat_types(_feat_types_of(domain))
-    B, m = int(nodes3.shape[0]), int(nodes3.shape[1])
-    if m > MAX_SAMPLE_TREES:
-        raise ValueError(f"leaf-space posterior samples support at most {MAX_SAMPLE_TREES} trees (got {m})")
-    noise = np.ascontiguousarray(np.asarray(noise, dtype=np.float64).reshape(-1))
-    scale = np.ascontiguousarray(np.asarray(scale, dtype=np.float64).reshape(-1))
-    if noise.shape[0] != B or scale.shape[0] != B:
-        raise ValueError(f"noise/scale must have one entry per forest ({B})")
-    R = posterior_sample_dim(nodes3, ft)
+    if nodes3.shape[1] > MAX_SAMPLE_TREES:
+        raise ValueError(f"leaf-space posterior samples support at most {MAX_SAMPLE_TREES} trees (got {nodes3.shape[1]})")
+    q = _leaf_inputs(nodes3, noise, scale, train_x, train_y, _feat_types_of(domain), candidates)
+    B, C, R, dev = q.B, q.C, q.R, q.device
     if R > MAX_SAMPLE_LEAVES:
         raise ValueError(f"leaf-space posterior samples support at most {MAX_SAMPLE_LEAVES} leaves per forest (got {R})")
     if eps is not None and tuple(eps.shape) != (B, S, R):
         raise ValueError(f"eps must have shape (B, num_samples, R) = {(B, S, R)}, got {tuple(eps.shape)}")
-    lib = _lib.lib()
-    Xd, _ = _points(train_x, ft.shape[0])
-    N, d = Xd.shape
-    dev = Xd.device
-    yd = _lib.to_device(train_y.detach() if _is_torch(train_y) else np.asarray(train_y, dtype=np.float64))
-    yd = yd.to(torch.float64).reshape(-1).contiguous()
-    if yd.shape[0] != N:
-        raise ValueError(f"y has {yd.shape[0]} rows, X has {N}")
-    cand_d, _ = _points(candidates, ft.shape[0])
-    C = int(cand_d.shape[0])
     code = _REDUCE[reduce]
     out_bytes = 8 * B * S * C if code == _lib.SAMPLE_FULL else 16 * B * S
     _check_output_budget(out_bytes + (8 * B * S * R if eps is None else 0),
@@ -181,8 +151,6 @@ def posterior_samples(model, data, candidates, domain, num_samples, *, generator
     else:
         eps_d = _lib.to_device(eps.detach() if _is_torch(eps) else np.asarray(eps, dtype=np.float64)).to(torch.float64)
         eps_d = eps_d.contiguous()
-    pf = packed_forest(nodes3, ft)
-    noise_d, scale_d = _lib.to_device(noise), _lib.to_device(scale)
     if code == _lib.SAMPLE_FULL:
         f = torch.empty((B, S, C), dtype=torch.float64, device=dev)
         red = idx = None
@@ -190,15 +158,10 @@ def posterior_samples(model, data, candidates, domain, num_samples, *, generator
         f = None
         red = torch.empty((B, S), dtype=torch.float64, device=dev)
         idx = torch.empty((B, S), dtype=torch.int64, device=dev)
-    info = torch.empty(B, dtype=torch.int32, device=dev)
-    need = lambda k: int(lib.bark_posterior_samples_workspace_bytes(N, R, pf.m, k, C, S))  # noqa: E731
-    Bc = int(chunk) if chunk else _fit_chunk(B, need)
-    ws = _lib.workspace(need(Bc))
-    _lib.check(lib.bark_posterior_samples_hip(_lib.ctx(), _lib.ptr(pf.packed), pf.info_ref, _lib.ptr(Xd), N, d, _lib.ptr(yd),
-                                              _lib.ptr(noise_d), _lib.ptr(scale_d), _lib.ptr(cand_d), C, _lib.ptr(eps_d), S,
-                                              code, _lib.ptr(f), _lib.ptr(red), _lib.ptr(idx), _lib.ptr(info), _lib.ptr(ws),
-                                              ws.numel(), Bc, _lib.stream_ptr()))
-    _raise_on_info(info, "leaf-space system")
+    lib = _lib.lib()
+    _leaf_call(q, lib.bark_posterior_samples_hip,
+               lambda k: int(lib.bark_posterior_samples_workspace_bytes(q.N, R, q.pf.m, k, C, S)), chunk,
+               _lib.ptr(q.cand_d), C, _lib.ptr(eps_d), S, code, _lib.ptr(f), _lib.ptr(red), _lib.ptr(idx))
     on_device = _is_torch(candidates)
     if code == _lib.SAMPLE_FULL:
         return f if on_device else f.cpu().numpy()

@@ -28,6 +28,7 @@ MARGIN = 1e-6
 VAR_FLOOR = 1e-3
 TILE = 256  # candidates per workgroup of acq_scan_kernel (bark_amd/csrc/acquire.hip)
 NODE_LIMIT = 255
+POSTERIOR_BLOCK = 2048  # candidates per call of the oracle (every case of CASES: one call)
 D_CONT = 4  # mixed_problem(d_cont=4, n_int=2, n_cat=2): d = 8; the complete trees split on the continuous columns
 
 
@@ -103,6 +104,11 @@ CASES = {c.name: c for c in [
 ]}
 
 
+# Two passes of the scan's candidate slab loop (65 536 candidates per slab) over two chunks of forests.  Not in CASES: among
+# so many candidates under 2-tree forests many share all their leaves, so no arg-min is MARGIN apart (precheck).
+SLAB_CASE = Case("slab_c65537", ("prior", 2), N=20, B=3, C=(1 << 16) + 1, chunk=2, seed=9)
+
+
 def resolve_R(case: Case):
     if case.forest[0] == "prior":
         return None
@@ -141,8 +147,9 @@ def problem(N, seed):
 
 
 @lru_cache(maxsize=None)
-def make_inputs(name: str) -> Inputs:
-    case = CASES[name]
+def make_inputs(name) -> Inputs:
+    """of a case of CASES by name, or of a Case"""
+    case = CASES[name] if isinstance(name, str) else name
     X, y, bounds, ft = problem(case.N, 100 + case.seed)
     cand, _, _, _ = problem(case.C, 200 + case.seed)
     rng = np.random.default_rng(case.seed)
@@ -162,19 +169,23 @@ def make_inputs(name: str) -> Inputs:
 
 
 @lru_cache(maxsize=None)
-def posterior(name: str):
+def posterior(name):
     """(mu, var) (B, C) of the oracle's dense route; computed once per case and shared"""
     inp = make_inputs(name)
-    mu, var = orc.forest_predict(inp.model, inp.data, inp.cand, inp.ft)
+    # the oracle forms the full (B, C, C) covariance before it takes the diagonal: blocks of candidates bound it (a
+    # candidate's posterior does not depend on the other candidates)
+    parts = [orc.forest_predict(inp.model, inp.data, inp.cand[i:i + POSTERIOR_BLOCK], inp.ft)
+             for i in range(0, inp.case.C, POSTERIOR_BLOCK)]
+    mu = np.concatenate([p[0] for p in parts], axis=1)
+    var = np.concatenate([p[1] for p in parts], axis=1)
     mu.setflags(write=False)
-    var = np.array(var)
     var.setflags(write=False)
     return mu, var
 
 
-def reference(name: str, kind: str, dtype=np.float64):
+def reference(name, kind: str, dtype=np.float64):
     mu, var = posterior(name)
-    return acquisition(mu, var, CASES[name].kappa, kind, dtype)
+    return acquisition(mu, var, make_inputs(name).case.kappa, kind, dtype)
 
 
 def precheck(name: str):

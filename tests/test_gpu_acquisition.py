@@ -109,6 +109,23 @@ def test_best_without_the_vector(scan, name, kind):
     assert index == int(np.argmin(acq)) and value == acq.min()
 
 
+@pytest.mark.parametrize("kind", ar.KINDS)
+def test_candidate_slabs(scan, kind):
+    """C = 65 537: the scan walks the candidates in two slabs (65 536 and 1) under each of two chunks of forests.  A
+    candidate's value does not depend on the other candidates, so each part equals a scan of that part alone, bit for bit."""
+    inp = ar.make_inputs(ar.SLAB_CASE)
+    C, slab = inp.case.C, 1 << 16
+    kw = dict(kappa=inp.case.kappa, kind=kind, return_values=True, chunk=inp.case.chunk)
+    value, index, acq = scan(inp.model, inp.data, inp.cand, inp.ft, **kw)
+    assert acq.shape == (C,) and acq.dtype == np.float64
+    used = bar_used(acq, ar.reference(ar.SLAB_CASE, kind))
+    print(f"{inp.case.name} {kind}: fraction of the bar used {used:.3g}")
+    assert used <= 1.0
+    assert np.array_equal(acq[:slab], scan(inp.model, inp.data, inp.cand[:slab], inp.ft, **kw)[2])
+    assert np.array_equal(acq[slab:], scan(inp.model, inp.data, inp.cand[slab:], inp.ft, **kw)[2])
+    assert index == int(np.argmin(acq)) and value == acq[index]
+
+
 def test_ties_go_to_the_lowest_index(scan):
     """exact duplicate rows: the winner of prior_n64 repeated in front of, inside and behind its own workgroup"""
     inp = ar.make_inputs("prior_n64")

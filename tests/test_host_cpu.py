@@ -30,6 +30,45 @@ def test_library_exports_every_declared_symbol():
     assert lib.bark_leaf_npad(1) == 128 and lib.bark_leaf_npad(128) == 128 and lib.bark_leaf_npad(129) == 256
 
 
+LEAF_WORKSPACE = {"mll": "bark_mll_leafspace_workspace_bytes", "inverse": "bark_kernel_inverse_leafspace_workspace_bytes",
+                  "samples": "bark_posterior_samples_workspace_bytes", "scan": "bark_acquisition_scan_workspace_bytes",
+                  "step": "bark_noise_scale_step_chains_workspace_bytes"}
+# (function, its arguments after bark_hip.h, bytes): mll (N, R, m, Bc, C), inverse (N, R, m, Bc), samples (N, R, m, Bc, C, S),
+# scan (N, R, m, Bc, C), step (N, R, m, nc).  The bytes are those of the library before the five functions shared one
+# layout; callers size buffers by them, so they are pinned.  Edges: N and R around the 128 block and the 32-bit code word,
+# R = 8192 (the limit), C around the scan's 65 536-candidate slab, S around the draws' padding steps, and the refusals (0).
+LEAF_WORKSPACE_BYTES = [
+    ("mll", (1, 1, 1, 1, 0), 201796352), ("mll", (127, 32, 50, 3, 0), 202734336),
+    ("mll", (128, 33, 50, 3, 1), 203333120), ("mll", (129, 128, 64, 64, 0), 231802368),
+    ("mll", (4097, 129, 50, 3, 65535), 210894080), ("mll", (129, 8192, 1, 1, 0), 743768832),
+    ("mll", (4097, 8192, 64, 1, 65536), 1896481536), ("mll", (128, 129, 50, 64, 65537), 395086336),
+    ("mll", (0, 32, 50, 3, 0), 0), ("mll", (128, 0, 50, 3, 0), 0), ("mll", (128, 32, 50, 0, 0), 0),
+    ("mll", (128, 32, 50, 3, -1), 0), ("inverse", (1, 1, 1, 1), 201985536), ("inverse", (127, 32, 50, 3), 203422464),
+    ("inverse", (128, 33, 64, 64), 246204928), ("inverse", (129, 128, 50, 3), 204113664),
+    ("inverse", (4097, 129, 50, 64), 592120832), ("inverse", (129, 8192, 1, 1), 1829700352),
+    ("inverse", (0, 32, 50, 3), 0), ("inverse", (128, 32, 50, 0), 0), ("samples", (1, 1, 1, 1, 1, 1), 202002432),
+    ("samples", (127, 32, 50, 3, 1, 16), 203352064), ("samples", (128, 33, 50, 3, 65535, 17), 205810432),
+    ("samples", (129, 128, 64, 64, 65536, 32), 346686976), ("samples", (4097, 129, 50, 3, 65537, 33), 212519424),
+    ("samples", (129, 8192, 1, 1, 1, 1), 1285555456), ("samples", (0, 32, 50, 3, 4, 4), 0),
+    ("samples", (128, 32, 50, 0, 4, 4), 0), ("samples", (128, 32, 50, 3, 0, 4), 0),
+    ("samples", (128, 32, 50, 3, 4, 0), 0), ("scan", (1, 1, 1, 1, 1), 201986816),
+    ("scan", (127, 32, 50, 3, 65535), 205701888), ("scan", (128, 33, 50, 3, 65536), 206494208),
+    ("scan", (129, 128, 64, 64, 65537), 325294336), ("scan", (4097, 129, 50, 3, 1), 207174912),
+    ("scan", (129, 8192, 1, 1, 65537), 2158466560), ("scan", (0, 32, 50, 3, 4), 0), ("scan", (128, 32, 50, 0, 4), 0),
+    ("scan", (128, 32, 50, 3, 0), 0), ("step", (1, 1, 1, 1), 201986304), ("step", (127, 32, 50, 3), 203426048),
+    ("step", (128, 33, 64, 64), 246271232), ("step", (129, 128, 50, 3), 204117504),
+    ("step", (4097, 129, 50, 64), 594219264), ("step", (129, 8192, 1, 1), 1829702144), ("step", (0, 32, 50, 3), 0),
+    ("step", (128, 32, 50, 0), 0),
+]
+
+
+def test_leafspace_workspace_sizes_are_pinned():
+    lib = _lib.lib()
+    for which, args, want in LEAF_WORKSPACE_BYTES:
+        assert int(getattr(lib, LEAF_WORKSPACE[which])(*args)) == want, (which, args)
+    assert {w for w, _, _ in LEAF_WORKSPACE_BYTES} == set(LEAF_WORKSPACE)
+
+
 @pytest.mark.parametrize("name", ["g1_kat_tree", "g3_prior_mixed_n64", "g5_boundaries", "g7_tree_function"])
 def test_packer_wire_format_reproduces_reference_leaves(name):
     g = load_golden(name)
