@@ -140,6 +140,9 @@ SIGNATURES = {
     "bark_acquisition_plan": (ci, [i64, i64, ci, ctypes.POINTER(ci), ctypes.POINTER(i64)]),
     "bark_acquisition_scan_hip": (ci, [vp, vp, ctypes.POINTER(PackInfo), vp, i64, i64, vp, vp, vp, vp, i64, ctypes.c_double, ci, ci,
                                        vp, vp, vp, vp, vp, ctypes.c_size_t, i64, vp]),
+    "bark_acquisition_scan_pending_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64, i64, i64]),
+    "bark_acquisition_scan_pending_hip": (ci, [vp, vp, ctypes.POINTER(PackInfo), vp, i64, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64,
+                                               ctypes.c_double, ci, ci, vp, vp, vp, vp, vp, ctypes.c_size_t, i64, vp]),
     "bark_lowrank_workspace_bytes": (ctypes.c_size_t, [i64, i64]),
     "bark_lowrank_update_hip": (ci, [vp, i64, vp, i64, ci, ci, vp, vp, vp, ctypes.c_size_t, vp]),
     "bark_lowrank_swap_eval_hip": (ci, [vp, i64, vp, i64, i64, vp, vp, vp, ctypes.c_size_t, vp]),

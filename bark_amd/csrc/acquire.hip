@@ -5,7 +5,8 @@
 // leaves L(x) = a_0 < a_1 < ... (bits of its one-hot code, i.e. tree order):
 //     mu_b(x)  = c_b * sum_i w_b[a_i]
 //     var_b(x) = (scale_b / m) * ( sum_i Minv[a_i][a_i] + 2 * sum_i ( sum_{j < i} Minv[a_j][a_i] ) )
-// Only the upper triangle of M^-1 is read, m (m + 1) / 2 entries instead of leaf_predict_kernel's m^2.  Three kernels:
+// Only the upper triangle of M^-1 is read, m (m + 1) / 2 entries instead of leaf_predict_kernel's m^2.  The kernels:
+//   acq_condition_kernel  optional: M^-1 conditioned on the pending points (rank-one downdates), before anything reads it
 //   acq_pack_kernel     upper triangle of M^-1, rows packed, followed by w: the image acq_scan_kernel stages in LDS
 //   acq_scan_kernel     one thread per candidate; the forests of the chunk in order, three running sums per candidate in
 //                       registers (sum of mu - kappa sd, of mu, of var + mu^2), kept in a (3, C) buffer between chunks
@@ -21,6 +22,7 @@ namespace {
 constexpr int ACQ_TILE = 256;                  // candidates per workgroup, one per thread
 constexpr size_t ACQ_LDS_MAX = 160 * 1024;     // all of a CU's LDS: one workgroup per CU
 constexpr int ACQ_MAX_TREES = 64;
+constexpr int ACQ_COND_THREADS = 1024;         // acq_condition_kernel: one workgroup per forest
 
 // Image (bc, tri + R): row a of the upper triangle of M^-1 at a (2R - a - 1) / 2 + a, i.e. entry (a, b >= a) at
 // a (2R - a - 1) / 2 + b; then w.
@@ -34,6 +36,68 @@ __global__ __launch_bounds__(256) void acq_pack_kernel(const double *__restrict_
     for (int c = a + threadIdx.x; c < R; c += 256) dst[base + c] = row[c];
     if (a == 0)
         for (int c = threadIdx.x; c < R; c += 256) dst[tri + c] = w[(size_t)b * R + c];
+}
+
+// Conditioning on P pending points ("kriging believer": the fantasised observation at a pending point x* is the forest's own
+// posterior mean there, so w does not change and only M^-1 does).  With z the one-hot row of x* (leaves a_0 < a_1 < ... in
+// code-bit order) and c = scale / (m s2), per point, in the order given, each update seeing the previous one:
+//     t = M^-1 z   (t_i = sum_k Minv[i][a_k], k in code-bit order),   q = z't = sum_k t[a_k]   (one wave, a fixed butterfly)
+//     Minv[i][j] -= g (t_i t_j),   g = c / (1 + c q)
+// over the full matrix; (i, j) and (j, i) subtract the same product, so a symmetric M^-1 stays symmetric in bits.  One
+// workgroup per forest of the chunk: nothing crosses workgroups, every hand-over is a workgroup barrier (which also orders the
+// workgroup's global stores before its later loads).  Forests whose sweep failed (info != 0) are left alone.
+// LDS (8-byte items only): t [R], q, then the point's leaf list [ACQ_MAX_TREES] and its length.
+__global__ __launch_bounds__(ACQ_COND_THREADS) void acq_condition_kernel(const uint32_t *__restrict__ pcodes, int W, int ppad,
+                                                                         int P, double *Minv, int R,
+                                                                         const double *__restrict__ noise,
+                                                                         const double *__restrict__ scale, int m,
+                                                                         const int32_t *__restrict__ info) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+    if (info[b] != 0) return;  // the whole workgroup: no barrier is left waiting
+    double *t = smem;
+    double *qs = smem + R;
+    int *leaves = reinterpret_cast<int *>(smem + R + 1);
+    int *count = leaves + ACQ_MAX_TREES;
+    double *Mb = Minv + (size_t)b * R * R;
+    const double c = scale[b] / ((double)m * (1e-6 + noise[b]));
+    for (int p = 0; p < P; ++p) {
+        if (tid == 0) {
+            int cnt = 0;
+            for (int w0 = 0; w0 < W; ++w0) {
+                uint32_t bits = pcodes[((size_t)b * W + w0) * ppad + p];
+                while (bits) {  // bits in increasing order: tree order
+                    const int a = 32 * w0 + __builtin_ctz(bits);
+                    if (cnt < ACQ_MAX_TREES && a < R) leaves[cnt++] = a;
+                    bits &= bits - 1;
+                }
+            }
+            *count = cnt;
+        }
+        __syncthreads();
+        const int cnt = *count;
+        for (int i = tid; i < R; i += ACQ_COND_THREADS) {
+            const double *row = Mb + (size_t)i * R;
+            double s = 0.0;
+            for (int k = 0; k < cnt; ++k) s += row[leaves[k]];
+            t[i] = s;
+        }
+        __syncthreads();
+        if (wave == 0) {
+            double v = lane < cnt ? t[leaves[lane]] : 0.0;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+            if (lane == 0) *qs = v;
+        }
+        __syncthreads();
+        const double g = c / (1.0 + c * *qs);
+        for (int i = wave; i < R; i += ACQ_COND_THREADS / 64) {
+            const double ti = t[i];
+            double *row = Mb + (size_t)i * R;
+            for (int j = lane; j < R; j += 64) row[j] -= g * (ti * t[j]);
+        }
+        __syncthreads();  // the next point reads the updated matrix and reuses t and the leaf list
+    }
 }
 
 // LDS_TABLE: the forest's image sits in LDS ([tri + R] doubles) in front of the tile's leaf lists ([m][ACQ_TILE] 16-bit
@@ -147,8 +211,10 @@ constexpr long long ACQ_NO_INDEX = 0x7fffffffffffffffLL;
 
 // kind 0: mean over the forests of mu - kappa sd (the reference's calculate_acqf, tests/optimization/test_optimality.py);
 // kind 1: the lower confidence bound of the moment-matched mixture (tree_gps.py:116-131)
+// skip (n_skip entries): candidates that keep their value in acq_out but never win the minimum
 __global__ __launch_bounds__(256) void acq_finish_kernel(const double *__restrict__ acc, long long C, int B, double kappa,
-                                                         int kind, double *__restrict__ acq_out, double *__restrict__ part_v,
+                                                         int kind, const long long *__restrict__ skip, int n_skip,
+                                                         double *__restrict__ acq_out, double *__restrict__ part_v,
                                                          long long *__restrict__ part_i) {
     __shared__ double rv[4];
     __shared__ long long ri[4];
@@ -165,6 +231,11 @@ __global__ __launch_bounds__(256) void acq_finish_kernel(const double *__restric
         }
         if (acq_out) acq_out[c] = v;
         i = c;
+        for (int k = 0; k < n_skip; ++k)
+            if (skip[k] == c) {
+                v = INFINITY;
+                i = ACQ_NO_INDEX;
+            }
     }
     block_min(v, i, rv, ri);
     if (threadIdx.x == 0) {
@@ -173,7 +244,8 @@ __global__ __launch_bounds__(256) void acq_finish_kernel(const double *__restric
     }
 }
 
-// one workgroup: the minimum over the partials; NaN / -1 when a forest of the call failed (info != 0) or no value is finite
+// one workgroup: the minimum over the partials; NaN / -1 when a forest of the call failed (info != 0), no value is finite or
+// every candidate was skipped
 __global__ __launch_bounds__(256) void acq_best_kernel(const double *__restrict__ part_v, const long long *__restrict__ part_i,
                                                        int nblk, const int32_t *__restrict__ info, int B,
                                                        double *__restrict__ best, long long *__restrict__ best_i) {
@@ -205,8 +277,19 @@ size_t scan_lds_bytes(int64_t R, int64_t m, bool lds_table) {
 
 const void *acq_scan_lds_kernel_ptr() { return reinterpret_cast<const void *>(acq_scan_kernel<true>); }
 size_t acq_lds_max() { return ACQ_LDS_MAX; }
+const void *acq_condition_kernel_ptr() { return reinterpret_cast<const void *>(acq_condition_kernel); }
+size_t acq_condition_lds_bytes(int64_t R) { return ((size_t)R + 1) * sizeof(double) + (ACQ_MAX_TREES + 2) * sizeof(int); }
 int64_t acq_partials(int64_t C) { return (C + 255) / 256; }
 size_t acq_table_doubles(int64_t R) { return (size_t)R * (R + 1) / 2 + R; }
+
+// M^-1 of the chunk's forests conditioned on the P pending points whose codes are pcodes (bc, W, ppad)
+int acq_condition(const uint32_t *pcodes, int W, int ppad, int P, double *Minv, int R, const double *noise, const double *scale,
+                  int m, int bc, const int32_t *info, hipStream_t s) {
+    hipLaunchKernelGGL(acq_condition_kernel, dim3((unsigned)bc), dim3(ACQ_COND_THREADS), acq_condition_lds_bytes(R), s, pcodes, W,
+                       ppad, P, Minv, R, noise, scale, m, info);
+    BARK_LAUNCH_CHECK();
+    return BARK_OK;
+}
 
 // image of the chunk for the LDS variant
 int acq_pack(const double *Minv, const double *w, int R, int bc, double *tab, hipStream_t s) {
@@ -230,11 +313,11 @@ int acq_scan(int variant, const uint32_t *ccodes, int W, int cpad, int n, const 
     return BARK_OK;
 }
 
-int acq_finish(const double *acc, int64_t C, int B, double kappa, int kind, double *acq_out, double *part_v, int64_t *part_i,
-               const int32_t *info, double *best, int64_t *best_i, hipStream_t s) {
+int acq_finish(const double *acc, int64_t C, int B, double kappa, int kind, const int64_t *skip, int n_skip, double *acq_out,
+               double *part_v, int64_t *part_i, const int32_t *info, double *best, int64_t *best_i, hipStream_t s) {
     const int nblk = (int)acq_partials(C);
-    hipLaunchKernelGGL(acq_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, s, acc, (long long)C, B, kappa, kind, acq_out, part_v,
-                       reinterpret_cast<long long *>(part_i));
+    hipLaunchKernelGGL(acq_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, s, acc, (long long)C, B, kappa, kind,
+                       reinterpret_cast<const long long *>(skip), n_skip, acq_out, part_v, reinterpret_cast<long long *>(part_i));
     BARK_LAUNCH_CHECK();
     hipLaunchKernelGGL(acq_best_kernel, dim3(1), dim3(256), 0, s, part_v, reinterpret_cast<const long long *>(part_i), nblk, info, B,
                        best, reinterpret_cast<long long *>(best_i));

@@ -87,9 +87,14 @@ int acq_pack(const double *Minv, const double *w, int R, int bc, double *tab, hi
 int acq_scan(int variant, const uint32_t *ccodes, int W, int cpad, int n, const double *wvec, const double *Minv,
              const double *tab, int R, const double *noise, const double *scale, int m, int bc, double kappa, int first,
              double *acc, size_t astride, hipStream_t s);
-int acq_finish(const double *acc, int64_t C, int B, double kappa, int kind, double *acq_out, double *part_v, int64_t *part_i,
+int acq_condition(const uint32_t *pcodes, int W, int ppad, int P, double *Minv, int R, const double *noise, const double *scale,
+                  int m, int bc, const int32_t *info, hipStream_t s);
+int acq_finish(const double *acc, int64_t C, int B, double kappa, int kind, const int64_t *skip, int n_skip, double *acq_out,
+               double *part_v, int64_t *part_i,
                const int32_t *info, double *best, int64_t *best_i, hipStream_t s);
 const void *acq_scan_lds_kernel_ptr();
+const void *acq_condition_kernel_ptr();
+size_t acq_condition_lds_bytes(int64_t R);
 size_t acq_lds_max();
 int64_t acq_partials(int64_t C);
 size_t acq_table_doubles(int64_t R);
@@ -378,6 +383,7 @@ int set_lds_limits() {
         if (e == hipSuccess) e = set(reinterpret_cast<const void *>(solve_narrow_kernel<2, 1>), GEMM_LDS);
         if (e == hipSuccess) e = set(leaf_inverse_kernel_ptr(), LEAF_INV_LDS_MAX);
         if (e == hipSuccess) e = set(acq_scan_lds_kernel_ptr(), acq_lds_max());
+        if (e == hipSuccess) e = set(acq_condition_kernel_ptr(), acq_condition_lds_bytes(8192));
         status[dev] = (int)e;
     });
     if (status[dev] != 0)
@@ -1360,6 +1366,7 @@ struct LeafNeeds {
     int64_t scan = 0;         // acquisition scan over this many candidates: LDS image (Bc, tri + R), running sums (3, scan) and
                               // the per-workgroup minima of the finish
     bool chain_step = false;  // noise/scale step: new_mll and the sweep's info (Bc each), K^-1 y (Bc, N)
+    int64_t pending = 0;      // acquisition scan conditioned on this many pending points: their one-hot codes
 };
 
 // 256-byte aligned areas handed out front to back; base == nullptr: sizes only
@@ -1375,8 +1382,9 @@ struct Carve {
 
 struct LeafAreas {
     Layout L;  // the R x R sweep workspace (N := R; candidates := the R identity columns), at the front
-    int64_t R, Rpad, W, npad, cpad, Spad;
+    int64_t R, Rpad, W, npad, cpad, Spad, ppad;
     uint32_t *codes, *ccodes;    // one-hot leaf codes of the N points / of the resident candidates (Bc, W, npad | cpad)
+    uint32_t *pcodes;            // ... of the scan's pending points (Bc, W, ppad)
     unsigned long long *planes;  // bit planes of `codes` (Bc, 32 W, npad / 64)
     double *yy;                  // y'y
     double *Minv, *w, *Wm, *Wt;  // see LeafNeeds; an area the call does not need is empty
@@ -1398,6 +1406,7 @@ LeafAreas leaf_areas(void *workspace, int64_t N, int64_t R, int64_t m, int64_t B
     a.npad = round_up(N, NB);
     a.cpad = q.cand > 0 ? round_up(q.cand, NB) : 0;
     a.Spad = q.S > 0 ? sample_spad(q.S) : 0;
+    a.ppad = q.pending > 0 ? round_up(q.pending, NB) : 0;
     a.L = make_layout(R, q.identity ? R : 0, m, Bc);
     const size_t nb = (size_t)Bc;
     const size_t partials = nb * (q.S > 0 ? sample_partials(q.cand, q.S) : 0) + acq_partials(q.scan);
@@ -1417,6 +1426,7 @@ LeafAreas leaf_areas(void *workspace, int64_t N, int64_t R, int64_t m, int64_t B
     a.new_mll = cv.take<double>(q.chain_step ? nb : 0);
     a.sweep_info = cv.take<int32_t>(q.chain_step ? nb : 0);
     a.kinv_y = cv.take<double>(q.chain_step ? nb * N : 0);
+    a.pcodes = cv.take<uint32_t>(nb * a.W * a.ppad);
     a.total = cv.o;
     return a;
 }
@@ -1441,9 +1451,12 @@ LeafNeeds samples_needs(int64_t C, int64_t S) {  // draws need V and w, not M^-1
     q.S = S;
     return q;
 }
-LeafNeeds scan_needs(int64_t C) {  // the posterior's areas with the codes of one slab of candidates
+constexpr int64_t ACQ_MAX_PENDING = 64, ACQ_MAX_SKIP = 64;
+
+LeafNeeds scan_needs(int64_t C, int64_t P) {  // the posterior's areas with the codes of one slab of candidates
     LeafNeeds q = mll_needs(C < ACQ_SLAB ? C : ACQ_SLAB);
     q.scan = C;
+    q.pending = P;
     return q;
 }
 LeafNeeds chain_step_needs() {
@@ -1551,6 +1564,10 @@ struct LeafSystem {
     int walk_candidates(const double *cand, int64_t n) {
         return walk_one_hot(packed_c, &sub, cand, n, d, W, a.ccodes, ctx->fault, caller);
     }
+    // ... of the scan's P pending points -> a.pcodes
+    int walk_pending(const double *pending, int64_t P) {
+        return walk_one_hot(packed_c, &sub, pending, P, d, W, a.pcodes, ctx->fault, caller);
+    }
     // an invalid categorical value met by one of the chunk's walks goes into its forests' info
     int close_chunk() {
         hipLaunchKernelGGL(fault_info_kernel, dim3((unsigned)((bc + 255) / 256)), dim3(256), 0, caller, ctx->fault, sw->p.info, bc);
@@ -1585,7 +1602,12 @@ size_t bark_noise_scale_step_chains_workspace_bytes(int64_t N, int64_t max_bits,
 
 size_t bark_acquisition_scan_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t Bc, int64_t C) {
     if (N < 1 || max_bits < 1 || m < 1 || Bc < 1 || C < 1) return 0;
-    return leaf_areas(nullptr, N, max_bits, m, Bc, scan_needs(C)).total;
+    return leaf_areas(nullptr, N, max_bits, m, Bc, scan_needs(C, 0)).total;
+}
+
+size_t bark_acquisition_scan_pending_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t Bc, int64_t C, int64_t P) {
+    if (N < 1 || max_bits < 1 || m < 1 || Bc < 1 || C < 1 || P < 0 || P > ACQ_MAX_PENDING) return 0;
+    return leaf_areas(nullptr, N, max_bits, m, Bc, scan_needs(C, P)).total;
 }
 
 int bark_mll_leafspace_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d,
@@ -1684,14 +1706,20 @@ int bark_posterior_samples_hip(bark_ctx *ctx, const void *packed, const bark_pac
 }
 
 // Acquisition scan (include/bark_hip.h, kernels in acquire.hip): w and M^-1 of a chunk of forests are consumed by
-// acq_scan_kernel slab by slab of candidates before the next chunk is prepared; the finish after the last chunk.
-int bark_acquisition_scan_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d,
-                              const double *y, const double *noise, const double *scale, const double *cand, int64_t C,
-                              double kappa, int kind, int variant, double *acq_out, double *best_out, int64_t *idx_out,
-                              int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc, void *stream_) {
+// acq_scan_kernel slab by slab of candidates before the next chunk is prepared; the finish after the last chunk.  With pending
+// points M^-1 is conditioned on them first (acq_condition_kernel), so neither variant of the scan knows about them.
+int bark_acquisition_scan_pending_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N,
+                                      int64_t d, const double *y, const double *noise, const double *scale, const double *cand,
+                                      int64_t C, const double *pending, int64_t P, const int64_t *skip_idx, int64_t n_skip,
+                                      double kappa, int kind, int variant, double *acq_out, double *best_out, int64_t *idx_out,
+                                      int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc, void *stream_) {
     error_buffer()[0] = 0;
     if (!info || !scale || !cand || !best_out || !idx_out) return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: null argument");
     if (C < 1) return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: bad shape C=%lld", (long long)C);
+    if (P < 0 || P > ACQ_MAX_PENDING || n_skip < 0 || n_skip > ACQ_MAX_SKIP)
+        return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: at most %lld pending points and %lld skipped candidates (got %lld, %lld)",
+                    (long long)ACQ_MAX_PENDING, (long long)ACQ_MAX_SKIP, (long long)P, (long long)n_skip);
+    if ((P > 0 && !pending) || (n_skip > 0 && !skip_idx)) return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: null argument");
     if (kind != BARK_ACQ_LCB_MEAN && kind != BARK_ACQ_LCB_MIXTURE)
         return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: unknown kind %d", kind);
     if (!std::isfinite(kappa)) return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: kappa is not finite");
@@ -1699,12 +1727,18 @@ int bark_acquisition_scan_hip(bark_ctx *ctx, const void *packed, const bark_pack
     if ((rc = bark_acquisition_plan(info->max_bits, info->m, variant, &var, nullptr))) return rc;
     LeafSystem sys;
     rc = sys.open("bark_acquisition_scan_hip", ctx, packed, info, X, N, d, y, noise, info_out, workspace, workspace_bytes, Bc, C,
-                  scan_needs(C), stream_);
+                  scan_needs(C, P), stream_);
     if (rc) return rc;
     const LeafAreas &a = sys.a;
     rc = sys.for_chunks([&](int64_t c0) -> int {
         int r = sys.factor_chunk(noise + c0, scale + c0, info_out + c0, nullptr, 0);
         if (r || (r = sys.solve_w_minv())) return r;
+        if (P > 0) {
+            if ((r = sys.walk_pending(pending, P))) return r;
+            r = acq_condition(a.pcodes, sys.W, (int)a.ppad, (int)P, a.Minv, sys.R, noise + c0, scale + c0, sys.m, sys.bc,
+                              info_out + c0, sys.caller);
+            if (r) return r;
+        }
         if (var == 1 && (r = acq_pack(a.Minv, a.w, sys.R, sys.bc, a.tab, sys.caller))) return r;
         for (int64_t s0 = 0; s0 < C; s0 += ACQ_SLAB) {
             const int64_t n = C - s0 < ACQ_SLAB ? C - s0 : ACQ_SLAB;
@@ -1716,7 +1750,16 @@ int bark_acquisition_scan_hip(bark_ctx *ctx, const void *packed, const bark_pack
         return sys.close_chunk();
     });
     if (rc) return rc;
-    return acq_finish(a.acc, C, (int)sys.B, kappa, kind, acq_out, a.part, a.part_i, info_out, best_out, idx_out, sys.caller);
+    return acq_finish(a.acc, C, (int)sys.B, kappa, kind, skip_idx, (int)n_skip, acq_out, a.part, a.part_i, info_out, best_out, idx_out,
+                      sys.caller);
+}
+
+int bark_acquisition_scan_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d,
+                              const double *y, const double *noise, const double *scale, const double *cand, int64_t C,
+                              double kappa, int kind, int variant, double *acq_out, double *best_out, int64_t *idx_out,
+                              int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc, void *stream_) {
+    return bark_acquisition_scan_pending_hip(ctx, packed, info, X, N, d, y, noise, scale, cand, C, nullptr, 0, nullptr, 0, kappa, kind,
+                                             variant, acq_out, best_out, idx_out, info_out, workspace, workspace_bytes, Bc, stream_);
 }
 
 // The noise/scale half of the sampler step for nc chains (include/bark_hip.h): the MLL + inverse sequence for one chunk of nc

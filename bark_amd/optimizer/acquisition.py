@@ -21,11 +21,12 @@ import numpy as np
 
 from .. import _lib
 from ..fitting.mll import _feat_types_of, _forest3, _leaf_call, _leaf_inputs
-from ..forest import _is_torch
+from ..forest import _is_torch, _points
 
 KINDS = {"lcb_mean": _lib.ACQ_LCB_MEAN, "lcb_mixture": _lib.ACQ_LCB_MIXTURE}
 VARIANTS = {"auto": 0, "lds": 1, "global": 2}
 MAX_TREES, MAX_LEAVES = 64, 8192  # limits of the leaf-space posterior (include/bark_hip.h)
+MAX_PENDING = MAX_SKIP = 64  # limits of bark_acquisition_scan_pending_hip
 
 
 def acquisition_plan(max_bits: int, m: int, variant: str = "auto") -> dict:
@@ -39,8 +40,27 @@ def acquisition_plan(max_bits: int, m: int, variant: str = "auto") -> dict:
     return {"variant": ("lds", "global")[v.value - 1], "lds_bytes": int(nbytes.value)}
 
 
+def _skip_indices(skip, C: int):
+    """-> device int64 vector of the candidates to exclude, or None.  Host values are range-checked here; a device tensor
+    is taken as it is (no read-back: entries outside [0, C) have no effect in the kernel)."""
+    import torch
+
+    if _is_torch(skip) and skip.is_cuda:
+        t = skip.reshape(-1).to(torch.int64)
+    else:
+        arr = np.asarray(skip.cpu() if _is_torch(skip) else skip).reshape(-1)
+        if arr.size and not np.issubdtype(arr.dtype, np.integer):
+            raise ValueError(f"skip must hold integer candidate indices, got dtype {arr.dtype}")
+        if arr.size and (arr.min() < 0 or arr.max() >= C):
+            raise ValueError(f"skip indices must lie in [0, {C})")
+        t = _lib.to_device(arr.astype(np.int64))
+    if t.numel() > MAX_SKIP:
+        raise ValueError(f"at most {MAX_SKIP} candidates can be skipped (got {t.numel()})")
+    return t.contiguous() if t.numel() else None
+
+
 def acquisition_scan(model, data, candidates, domain, kappa: float = 1.96, kind: str = "lcb_mean",
-                     return_values: bool = False, chunk: int | None = None, variant: str = "auto"):
+                     return_values: bool = False, chunk: int | None = None, variant: str = "auto", pending=None, skip=None):
     """-> (best_value, best_index[, acq (C,)]): the minimum over the candidates of the acquisition and its index (ties:
     the lowest index); with `return_values` also the acquisition of every candidate.
 
@@ -55,6 +75,14 @@ def acquisition_scan(model, data, candidates, domain, kappa: float = 1.96, kind:
     `forest_predict(method="leafspace")`.  Measured 3.6x (B = 4, C = 10^4) to 15x (B = 256, C = 10^6) faster than that
     route plus a torch reduction, and not slower at any shape measured; below 65 536 candidates
     the scan does not fill the device (one workgroup per 256 candidates) and the shared leaf-space sweep sets the time.
+
+    pending: (P, d) points, numpy or torch, that are being evaluated already (P <= 64): every forest is conditioned on them
+    as if each had been observed at the forest's own posterior mean ("kriging believer"), so mu_b is the mean given the
+    real data and var_b the variance given the data and the pending points.  In leaf space that is one symmetric rank-one
+    downdate of the R x R matrix M^-1 per point and forest (include/bark_hip.h has the algebra); they are applied in the
+    order given, and two orders agree to rounding, not bit for bit.  skip: at most 64 candidate indices (sequence or
+    tensor) that keep their value in `acq` but never win the minimum; with every candidate skipped the result is
+    (NaN, -1).  With both None the call is the unconditioned scan, exactly as before.
 
     Torch candidates give device scalars (0-d tensors) and a device vector, numpy candidates a float, an int and a numpy
     vector.  ValueError for an invalid categorical value, LinAlgError for a forest whose leaf-space system is not positive
@@ -86,8 +114,19 @@ def acquisition_scan(model, data, candidates, domain, kappa: float = 1.96, kind:
     best = torch.empty((), dtype=torch.float64, device=dev)
     idx = torch.empty((), dtype=torch.int64, device=dev)
     lib = _lib.lib()
-    _leaf_call(q, lib.bark_acquisition_scan_hip, lambda k: int(lib.bark_acquisition_scan_workspace_bytes(q.N, R, q.pf.m, k, C)),
-               chunk, _lib.ptr(q.cand_d), C, kappa, KINDS[kind], VARIANTS[variant], _lib.ptr(acq), _lib.ptr(best), _lib.ptr(idx))
+    if pending is None and skip is None:
+        _leaf_call(q, lib.bark_acquisition_scan_hip, lambda k: int(lib.bark_acquisition_scan_workspace_bytes(q.N, R, q.pf.m, k, C)),
+                   chunk, _lib.ptr(q.cand_d), C, kappa, KINDS[kind], VARIANTS[variant], _lib.ptr(acq), _lib.ptr(best), _lib.ptr(idx))
+    else:
+        pend_d = None if pending is None or len(pending) == 0 else _points(pending, q.d)[0]
+        P = 0 if pend_d is None else int(pend_d.shape[0])
+        if P > MAX_PENDING:
+            raise ValueError(f"acquisition scan supports at most {MAX_PENDING} pending points (got {P})")
+        skip_d = None if skip is None else _skip_indices(skip, C)
+        _leaf_call(q, lib.bark_acquisition_scan_pending_hip,
+                   lambda k: int(lib.bark_acquisition_scan_pending_workspace_bytes(q.N, R, q.pf.m, k, C, P)), chunk,
+                   _lib.ptr(q.cand_d), C, _lib.ptr(pend_d), P, _lib.ptr(skip_d), 0 if skip_d is None else int(skip_d.numel()),
+                   kappa, KINDS[kind], VARIANTS[variant], _lib.ptr(acq), _lib.ptr(best), _lib.ptr(idx))
     if _is_torch(candidates):
         return (best, idx, acq) if return_values else (best, idx)
     out = (float(best.item()), int(idx.item()))
@@ -103,3 +142,48 @@ def propose_from_candidates(model, data, candidates, domain, kappa: float = 1.96
     if _is_torch(candidates):
         return candidates.index_select(0, idx.to(candidates.device).reshape(1))[0]
     return np.asarray(candidates)[idx]
+
+
+def propose_batch_from_candidates(model, data, candidates, domain, q: int, kappa: float = 1.96, kind: str = "lcb_mean",
+                                  pending=None, chunk: int | None = None, variant: str = "auto"):
+    """-> (rows (q, d), indices (q,)): q distinct candidate rows chosen greedily.  Pick k is the arg-min of the scan
+    conditioned on `pending` followed by picks 0 .. k-1 (`acquisition_scan(pending=..., skip=...)`), with those picks
+    excluded: a point that is being evaluated no longer attracts the next one, because its variance has collapsed.
+
+    A plain loop of q scans with no state kept between the picks, so the cost is q times one scan.  Torch candidates
+    give device tensors (a pick is gathered with index_select; no index is read back), numpy candidates numpy arrays.
+    ValueError for q < 1, q > C or P + q - 1 > 64 (the scan's limit on pending points)."""
+    C = len(candidates)
+    q = int(q)
+    P = 0 if pending is None else len(pending)
+    if q < 1 or q > C:
+        raise ValueError(f"q must lie in [1, {C}] (the number of candidates), got {q}")
+    if P + q - 1 > MAX_PENDING:
+        raise ValueError(f"pending points plus earlier picks exceed {MAX_PENDING} (P = {P}, q = {q})")
+    on_device = _is_torch(candidates)
+    if on_device:
+        import torch
+
+        pend = None if P == 0 else torch.as_tensor(pending, dtype=candidates.dtype, device=candidates.device)
+    else:
+        candidates = np.asarray(candidates)
+        pend = None if P == 0 else np.asarray(pending.cpu() if _is_torch(pending) else pending, dtype=np.float64)
+    rows, picks = [], []
+    for _ in range(q):
+        if on_device:
+            cur = pend if not rows else torch.cat(([] if pend is None else [pend]) + [torch.stack(rows)])
+            skip = torch.stack(picks) if picks else None
+        else:
+            cur = pend if not rows else np.concatenate(([] if pend is None else [pend]) + [np.stack(rows)])
+            skip = picks or None
+        _, idx = acquisition_scan(model, data, candidates, domain, kappa=kappa, kind=kind, chunk=chunk, variant=variant,
+                                  pending=cur, skip=skip)
+        if on_device:
+            idx = idx.to(candidates.device)
+            rows.append(candidates.index_select(0, idx.reshape(1))[0])
+        else:
+            rows.append(candidates[idx])
+        picks.append(idx)
+    if on_device:
+        return torch.stack(rows), torch.stack(picks)
+    return np.stack(rows), np.asarray(picks, dtype=np.int64)

@@ -381,6 +381,37 @@ int bark_acquisition_scan_hip(bark_ctx *ctx, const void *packed, const bark_pack
                               int64_t Bc, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Acquisition scan conditioned on pending points, with candidates excluded from the arg-min: what a batch of proposals
+ * needs ("these points are being evaluated already").  bark_acquisition_scan_hip is the P = 0, n_skip = 0 call of it.
+ * pending: (P, d) device, or NULL with P = 0.  Each pending point x* is treated as observed at the forest's own posterior
+ * mean ("kriging believer"), with the same noise.  With M = I_R + c Z'Z, w = M^-1 Z'y, c = scale / (m s2) as above and z the
+ * one-hot row of x* (its m leaves L(x*) set), per forest:
+ *     t = M^-1 z   (the sum of the m columns of M^-1 named by L(x*)),   q = z't,
+ *     M^-1 <- M^-1 - (c / (1 + c q)) t t',   w unchanged:
+ * the innovation y* - c z'w of the fantasised observation is zero, so w' = w + t (y* - c z'w) / (1 + c q) = w.  Hence
+ * mu_b(x) is the mean given the real data and var_b(x) the posterior variance of forest b given X and the pending points,
+ * i.e. what appending them to the training inputs gives (the variance depends on no y).  Nothing of size N or C is touched.
+ * Order (part of the contract): pending points in the order given, each update seeing the previous one; within a point the
+ * leaves in code-bit order; entries (i, j) and (j, i) subtract the same product.  Like the scan, the result depends neither
+ * on Bc nor on the variant, bit for bit; two orders of the same pending points agree to rounding only.
+ * skip_idx: (n_skip,) device int64 candidate indices, or NULL with n_skip = 0.  A listed candidate keeps its value in acq_out
+ * but never wins the minimum; entries outside [0, C) have no effect; with every candidate listed best_out / idx_out are
+ * NaN / -1.  An invalid categorical value in a pending point reports info_out[b] = -1, as in a candidate; forests with
+ * info_out[b] != 0 are not conditioned.
+ * Limits, refused with BARK_ERR_ARG before any launch: 0 <= P <= 64, 0 <= n_skip <= 64, and the scan's own.  The call only
+ * enqueues.  Extra memory over the scan: the codes of the pending points, Bc ceil(R / 32) 128 words when P > 0.
+ * As every leaf-space route the downdate loses digits as noise -> 0 (c grows, 1 + c q cancels against M^-1's own scale).
+ * ------------------------------------------------------------------------------------- */
+size_t bark_acquisition_scan_pending_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t Bc, int64_t C, int64_t P);
+int bark_acquisition_scan_pending_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N,
+                                      int64_t d, const double *y, const double *noise, const double *scale, const double *cand,
+                                      int64_t C, const double *pending /* (P, d) or NULL */, int64_t P,
+                                      const int64_t *skip_idx /* (n_skip,) or NULL */, int64_t n_skip, double kappa, int kind,
+                                      int variant, double *acq_out /* (C,) or NULL */, double *best_out /* 1 */,
+                                      int64_t *idx_out /* 1 */, int32_t *info_out /* (B,) */, void *workspace,
+                                      size_t workspace_bytes, int64_t Bc, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Woodbury / determinant-lemma updates — quick_inverse.py:13-33 (the per-tree step of the sampler,
  * bark_sampler.py:233-257).  With mul = -1 if `subtract` else +1:
  *   K_out         = K_inv - K_inv U (mul I + U' K_inv U)^-1 U' K_inv          (low_rank_inv_update)
