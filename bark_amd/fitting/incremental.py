@@ -20,7 +20,8 @@ import ctypes
 import numpy as np
 
 from .. import _lib
-from ..forest import _as_nodes, _feat_types, _is_torch, _points, _raise_on_categorical_fault, leaf_vectors_device, packed_forest
+from ..forest import _as_nodes, _feat_types, _is_torch, _raise_on_categorical_fault, leaf_vectors_device, packed_forest
+from . import _chains
 from .mll import _run_leafspace, batched_kernel_inverse
 
 MAX_RANK = 64  # leaf vectors one fused update can carry (lowrank.hip LR_MAX)
@@ -122,26 +123,32 @@ class ChainState:
     def __init__(self, K_inv, K_logdet, y):
         import torch
 
-        self.K_inv = _dev64(K_inv)
-        self.y = _dev64(y).reshape(-1).contiguous()
-        self.N = self.y.shape[0]
-        if self.K_inv.shape != (self.N, self.N):
-            raise ValueError(f"K_inv is {tuple(self.K_inv.shape)}, y has {self.N} rows")
-        self.logdet = float(K_logdet)
-        self.quad = _quadform(self.K_inv, self.y)
+        K_inv, y = _dev64(K_inv), _dev64(y).reshape(-1).contiguous()
+        N = y.shape[0]
+        if K_inv.shape != (N, N):
+            raise ValueError(f"K_inv is {tuple(K_inv.shape)}, y has {N} rows")
+        self._setup(K_inv, y, N, _quadform(K_inv, y), float(K_logdet), None,
+                    torch.empty(2, dtype=torch.float64, device=K_inv.device))
+
+    def _setup(self, K_inv, y, N, quad, logdet, X_seen, scalars):
+        """Every field of a state: `__init__` and `_view_of_chain` both end here."""
+        self.K_inv, self.y, self.N = K_inv, y, N
+        self.quad, self.logdet = quad, logdet
         self._pending = None
         self._ws = {}  # rank -> workspace tensor, reused across proposals
-        self._X_seen = None  # (caller's X object, device tensor) of the last propose_tree
-        self._scalars = torch.empty(2, dtype=torch.float64, device=self.K_inv.device)
+        self._X_seen = X_seen  # (caller's X object, device tensor) of the last propose_tree
+        self._scalars = scalars
 
-    def _workspace(self, r: int):
-        import torch
+    @classmethod
+    def _view_of_chain(cls, K_inv, y, N, quad, logdet, Xd, scalars):
+        """A state that is a VIEW of one chain of a `ChainBatch`: its slice of K_inv and of the scalars, the batch's y and
+        device X, and the quad / logdet the batch already holds (nothing is recomputed, nothing is copied)."""
+        st = cls.__new__(cls)
+        st._setup(K_inv, y, N, quad, logdet, (Xd, Xd), scalars)
+        return st
 
-        ws = self._ws.get(r)
-        if ws is None:
-            nbytes = int(_lib.lib().bark_tree_swap_workspace_bytes(self.N, r))  # >= the plain low-rank layout
-            ws = self._ws[r] = torch.empty(nbytes, dtype=torch.uint8, device=self.K_inv.device)
-        return ws
+    def _workspace(self, r: int):  # the tree-swap layout is >= the plain low-rank one: it serves both
+        return _chains.workspace(self._ws, r, lambda: _lib.lib().bark_tree_swap_workspace_bytes(self.N, r), self.K_inv.device)
 
     @classmethod
     def from_forest(cls, forest, noise, scale, X, y, feat_types):
@@ -249,15 +256,6 @@ class ChainState:
             self.quad, self.logdet = quad, logdet
         self._pending = None
 
-    def _points_of(self, X, ft):
-        if self._X_seen is None or self._X_seen[0] is not X:
-            Xd, _ = _points(X, ft.shape[0])
-            self._X_seen = (X, Xd)
-        Xd = self._X_seen[1]
-        if Xd.shape[0] != self.N:
-            raise ValueError(f"X has {Xd.shape[0]} rows, the chain has {self.N} points")
-        return Xd
-
     def propose_tree(self, old_nodes, new_nodes, X, feat_types, scale: float, m: int) -> float:
         """bark_sampler.py:233-256 from the two trees themselves: both are walked on the GPU and their one-hot
         leaf code, scaled by s_sqrtm = sqrt(scale / m), is the [U_old U_new] of `propose` (one column per leaf;
@@ -266,16 +264,14 @@ class ChainState:
         reference).  `accept()` commits as usual."""
         lib = _lib.lib()
         ft = _feat_types(feat_types)
-        Xd = self._points_of(X, ft)
+        Xd = _chains.points_of(self, X, ft, "chain has")
         old, new = _as_nodes(old_nodes, 1), _as_nodes(new_nodes, 1)
         if old.ndim != 1 or new.ndim != 1 or old.shape != new.shape:
             raise ValueError(f"trees must be (node_limit,) records of one container, got {old.shape} and {new.shape}")
         s = float(np.sqrt(scale / m))
-        info_old = _lib.PackInfo()
-        _lib.check(lib.bark_forest_pack_info(_lib.ptr(old), 1, 1, old.shape[0], _lib.ptr(ft), ft.shape[0],
-                                             ctypes.byref(info_old)))
+        r_old = int(_chains.leaf_counts(old, ft))
         pf = packed_forest(np.stack([old, new])[None], ft)
-        r, r_old = int(pf.info.max_bits), int(info_old.max_bits)
+        r = int(pf.info.max_bits)
         if r > MAX_RANK:
             U, U_new, r_old, r_new = _reached_leaf_vectors(old, new, Xd, ft, s)
             if U_new is None:
@@ -331,46 +327,21 @@ class ChainBatch:
         """quick_inverse.py:37-38 for every chain."""
         return 0.5 * (-self.quad - self.logdet)
 
-    def _points_of(self, X, ft):
-        if self._X_seen is None or self._X_seen[0] is not X:
-            Xd, _ = _points(X, ft.shape[0])
-            self._X_seen = (X, Xd)
-        Xd = self._X_seen[1]
-        if Xd.shape[0] != self.N:
-            raise ValueError(f"X has {Xd.shape[0]} rows, the chains have {self.N} points")
-        return Xd
-
     def _workspace(self, r: int, extra: int = 0):
-        import torch
-
-        key = (r, extra)
-        ws = self._ws.get(key)
-        if ws is None:
-            nbytes = int(_lib.lib().bark_tree_swap_chains_workspace_bytes(self.N, r, self.nc, None)) + extra
-            ws = self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.K_inv.device)
-        return ws
-
-    def _old_leaf_counts(self, old, ft):
-        lib = _lib.lib()
-        r_old = np.empty(old.shape[0], dtype=np.int64)
-        info_one = _lib.PackInfo()
-        for b in range(old.shape[0]):  # leaves of each old tree alone = the split between removed and added columns
-            _lib.check(lib.bark_forest_pack_info(_lib.ptr(np.ascontiguousarray(old[b])), 1, 1, old.shape[1], _lib.ptr(ft),
-                                                 ft.shape[0], ctypes.byref(info_one)))
-            r_old[b] = info_one.max_bits
-        return r_old
+        query = lambda: int(_lib.lib().bark_tree_swap_chains_workspace_bytes(self.N, r, self.nc, None)) + extra
+        return _chains.workspace(self._ws, (r, extra), query, self.K_inv.device)
 
     def propose_trees(self, old_trees, new_trees, X, feat_types, scale, m: int) -> np.ndarray:
         """bark_sampler.py:233-256 for one tree per chain: old_trees / new_trees (chains, node_limit) records,
         scale (chains,) -> the (chains,) MLL values the chains would have.  `accept(mask)` commits."""
         lib = _lib.lib()
         ft = _feat_types(feat_types)
-        Xd = self._points_of(X, ft)
+        Xd = _chains.points_of(self, X, ft, "chains have")
         old, new = _as_nodes(old_trees, 2), _as_nodes(new_trees, 2)
         if old.shape != new.shape or old.ndim != 2 or old.shape[0] != self.nc:
             raise ValueError(f"trees must be (chains, node_limit) records, got {old.shape} and {new.shape}")
-        scale = np.broadcast_to(np.asarray(scale, dtype=np.float64).reshape(-1), (self.nc,))
-        r_old = self._old_leaf_counts(old, ft)
+        scale = _chains.broadcast_scale(scale, self.nc)
+        r_old = _chains.leaf_counts(old, ft)  # leaves of each old tree alone = the split between removed and added columns
         pf = packed_forest(np.stack([old, new], axis=1), ft)  # (chains, 2, L): one [old, new] pair per chain
         r = int(pf.info.max_bits)
         if r > MAX_RANK:
@@ -394,10 +365,8 @@ class ChainBatch:
         (reached-leaf vectors, then the reference's subtract-then-add chain) on its own slice of K_inv."""
         states, vals = [], np.empty(self.nc)
         for b in range(self.nc):
-            st = ChainState.__new__(ChainState)
-            st.K_inv, st.y, st.N = self.K_inv[b], self.y, self.N
-            st.quad, st.logdet = float(self.quad[b]), float(self.logdet[b])
-            st._pending, st._ws, st._X_seen, st._scalars = None, {}, (Xd, Xd), self._scalars[b]
+            st = ChainState._view_of_chain(self.K_inv[b], self.y, self.N, float(self.quad[b]), float(self.logdet[b]), Xd,
+                                           self._scalars[b])
             vals[b] = st.propose_tree(old[b], new[b], Xd, ft, float(scale[b]), m)
             states.append(st)
         self._pending = ("states", states)
@@ -440,80 +409,57 @@ class ChainBatch:
         <= 16 leaves per pair); same state, same decision rule, K_inv equal to rounding (it sums in another order).  It
         reads K_inv by columns and updates (i, j) and (j, i) by the same amount, so K_inv must be exactly symmetric on entry — it
         is after `from_forests`, it need not be after a method="launches" sweep or `step_noise_scale` — and then stays so.  Outside its limits it raises ValueError — it never falls back."""
-        import torch
-
         if method not in ("launches", "resident"):
             raise ValueError(f"unknown method {method!r} (use 'launches' or 'resident')")
-        lib = _lib.lib()
         ft = _feat_types(feat_types)
-        Xd = self._points_of(X, ft)
-        old, new = _as_nodes(old_trees, 3), _as_nodes(new_trees, 3)
-        if old.shape != new.shape or old.ndim != 3 or old.shape[0] != self.nc:
-            raise ValueError(f"trees must be (chains, steps, node_limit) records, got {old.shape} and {new.shape}")
+        Xd = _chains.points_of(self, X, ft, "chains have")
+        old, new = _chains.check_step_trees(old_trees, new_trees, self.nc)
         steps = old.shape[1]
-        lq = np.ascontiguousarray(np.asarray(log_q_prior, dtype=np.float64).reshape(self.nc, steps).T)  # (steps, chains)
-        lu = np.ascontiguousarray(np.asarray(log_u, dtype=np.float64).reshape(self.nc, steps).T)
-        scale = np.broadcast_to(np.asarray(scale, dtype=np.float64).reshape(-1), (self.nc,))
-        infos = (_lib.PackInfo * steps)()
-        r_old = np.empty((steps, self.nc), dtype=np.int64)
-        sizes, pairs = [], []
-        for t in range(steps):
-            pair = np.ascontiguousarray(np.stack([old[:, t], new[:, t]], axis=1))  # (chains, 2, L)
-            pairs.append(pair)
-            _lib.check(lib.bark_forest_pack_info(_lib.ptr(pair), self.nc, 2, pair.shape[2], _lib.ptr(ft), ft.shape[0],
-                                                 ctypes.byref(infos[t])))
-            sizes.append(int(infos[t].packed_bytes))
-            r_old[t] = self._old_leaf_counts(old[:, t], ft)
-        r_max = max(int(infos[t].max_bits) for t in range(steps))
+        lq, lu = _chains.steps_major(log_q_prior, self.nc, steps), _chains.steps_major(log_u, self.nc, steps)
+        scale = _chains.broadcast_scale(scale, self.nc)
+        infos, offsets, _, host = _chains.pack_steps_host([np.stack([old[:, t], new[:, t]], axis=1) for t in range(steps)], ft)
+        r_old = np.ascontiguousarray(_chains.leaf_counts(old, ft).T)  # (steps, chains): the split between removed and added columns
+        r_max = max(int(info.max_bits) for info in infos)
         if method == "resident":
             plan = sweep_plan(self.N, r_max, int(Xd.shape[1]), nc=self.nc,
-                              max_nodes_bytes=max(2 * int(infos[t].stride) * 16 for t in range(steps)))
+                              max_nodes_bytes=max(2 * int(info.stride) * 16 for info in infos))
             if not plan["variant"]:
                 raise ValueError(f"sweep_trees(method=\"resident\"): {plan['reason']}; use method=\"launches\"")
         if r_max > MAX_RANK:
             raise ValueError(f"sweep_trees supports at most {MAX_RANK} leaves per [old, new] pair (got {r_max}); "
                              "use propose_trees / accept for this sweep")
-        offsets = np.zeros(steps, dtype=np.int64)
-        offsets[1:] = np.cumsum([(sz + 255) // 256 * 256 for sz in sizes[:-1]])
-        host = torch.empty(int(offsets[-1]) + sizes[-1], dtype=torch.uint8)
-        for t in range(steps):
-            _lib.check(lib.bark_forest_pack(_lib.ptr(pairs[t]), _lib.ptr(ft), ft.shape[0], ctypes.byref(infos[t]),
-                                            ctypes.c_void_p(host.data_ptr() + int(offsets[t]))))
-        packed = host.to(self.K_inv.device)
-        lq_d, lu_d = _lib.to_device(lq), _lib.to_device(lu)
+        packed, lq_d, lu_d, accept = _chains.upload_sweep(host, lq, lu)
         state = _lib.to_device(np.ascontiguousarray(np.stack([self.quad, self.logdet], axis=1)))
-        accept = torch.empty((steps, self.nc), dtype=torch.int32, device=self.K_inv.device)
         s_sqrtm = np.ascontiguousarray(np.sqrt(scale / m))
-        if method == "resident":
-            table = np.empty(int(lib.bark_tree_sweep_resident_table_bytes(steps, self.nc)) // 8, dtype=np.int64)
-            _lib.check(lib.bark_tree_sweep_resident_table(_lib.ptr(offsets), ctypes.cast(infos, ctypes.c_void_p), _lib.ptr(r_old),
-                                                          steps, self.nc, _lib.ptr(table)))
-            table_d, s_d = _lib.to_device(table), _lib.to_device(s_sqrtm)
-            key = ("resident", r_max)
-            ws = self._ws.get(key)
-            if ws is None:
-                nbytes = int(lib.bark_tree_sweep_resident_workspace_bytes(self.N, r_max, self.nc))
-                ws = self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.K_inv.device)
-            _lib.check(lib.bark_tree_sweep_resident_hip(_lib.ctx(), _lib.ptr(self.K_inv), self.N, self.nc, steps, _lib.ptr(packed),
-                                                        _lib.ptr(table_d), _lib.ptr(Xd), Xd.shape[1], _lib.ptr(s_d),
-                                                        _lib.ptr(self.y), _lib.ptr(lq_d), _lib.ptr(lu_d), _lib.ptr(state),
-                                                        _lib.ptr(accept), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
-            return self._finish_sweep(accept, state, ft)
+        launch = self._sweep_resident if method == "resident" else self._sweep_launches
+        return launch(steps, infos, offsets, r_old, r_max, s_sqrtm, Xd, packed, lq_d, lu_d, state, accept, ft)
+
+    def _sweep_launches(self, steps, infos, offsets, r_old, r_max, s_sqrtm, Xd, packed, lq_d, lu_d, state, accept, ft):
         ws = self._workspace(r_max, extra=16 * self.nc)
-        _lib.check(lib.bark_tree_sweep_chains_hip(_lib.ctx(), _lib.ptr(self.K_inv), self.N, self.nc, steps, _lib.ptr(packed),
-                                                  _lib.ptr(offsets), ctypes.cast(infos, ctypes.c_void_p), _lib.ptr(Xd), Xd.shape[1],
-                                                  _lib.ptr(r_old), _lib.ptr(s_sqrtm), _lib.ptr(self.y), _lib.ptr(lq_d),
-                                                  _lib.ptr(lu_d), _lib.ptr(state), _lib.ptr(accept), _lib.ptr(ws), ws.numel(),
-                                                  _lib.stream_ptr()))
+        _lib.check(_lib.lib().bark_tree_sweep_chains_hip(_lib.ctx(), _lib.ptr(self.K_inv), self.N, self.nc, steps, _lib.ptr(packed),
+                                                         _lib.ptr(offsets), ctypes.cast(infos, ctypes.c_void_p), _lib.ptr(Xd),
+                                                         Xd.shape[1], _lib.ptr(r_old), _lib.ptr(s_sqrtm), _lib.ptr(self.y),
+                                                         _lib.ptr(lq_d), _lib.ptr(lu_d), _lib.ptr(state), _lib.ptr(accept),
+                                                         _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+        return self._finish_sweep(accept, state, ft)
+
+    def _sweep_resident(self, steps, infos, offsets, r_old, r_max, s_sqrtm, Xd, packed, lq_d, lu_d, state, accept, ft):
+        lib = _lib.lib()
+        table = np.empty(int(lib.bark_tree_sweep_resident_table_bytes(steps, self.nc)) // 8, dtype=np.int64)
+        _lib.check(lib.bark_tree_sweep_resident_table(_lib.ptr(offsets), ctypes.cast(infos, ctypes.c_void_p), _lib.ptr(r_old),
+                                                      steps, self.nc, _lib.ptr(table)))
+        table_d, s_d = _lib.to_device(table), _lib.to_device(s_sqrtm)
+        ws = _chains.workspace(self._ws, ("resident", r_max),
+                               lambda: lib.bark_tree_sweep_resident_workspace_bytes(self.N, r_max, self.nc), self.K_inv.device)
+        _lib.check(lib.bark_tree_sweep_resident_hip(_lib.ctx(), _lib.ptr(self.K_inv), self.N, self.nc, steps, _lib.ptr(packed),
+                                                    _lib.ptr(table_d), _lib.ptr(Xd), Xd.shape[1], _lib.ptr(s_d),
+                                                    _lib.ptr(self.y), _lib.ptr(lq_d), _lib.ptr(lu_d), _lib.ptr(state),
+                                                    _lib.ptr(accept), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
         return self._finish_sweep(accept, state, ft)
 
     def _finish_sweep(self, accept, state, ft) -> np.ndarray:
-        acc = accept.cpu().numpy()  # the one synchronisation of the sweep
-        st = state.cpu().numpy()
-        # the device has already rewritten K_inv for every accepted step: take the running quad / logdet that belong to
-        # it BEFORE raising, so a caller that catches the error keeps a consistent batch (a singular chain is latched
-        # at -1 by decide_kernel and stays at the state after its last accepted step)
-        self.quad, self.logdet = st[:, 0].copy(), st[:, 1].copy()
+        # a singular chain is latched at -1 by decide_kernel and stays at the state after its last accepted step
+        acc, self.quad, self.logdet = _chains.read_decisions(accept, state)
         self._pending = None
         self.last_accept = acc.T.copy()
         _raise_on_categorical_fault(ft)
@@ -532,18 +478,13 @@ class ChainBatch:
 
         lib = _lib.lib()
         ft = _feat_types(feat_types)
-        Xd = self._points_of(X, ft)
+        Xd = _chains.points_of(self, X, ft, "chains have")
         nodes = _as_nodes(forests, 3)
         if nodes.ndim != 3 or nodes.shape[0] != self.nc:
             raise ValueError(f"forests must be (chains, m, node_limit) records of {self.nc} chains, got {nodes.shape}")
         if nodes.shape[1] > 1280:
             raise ValueError(f"step_noise_scale supports at most 1280 trees (got {nodes.shape[1]})")
-        vecs = []
-        for name, v in (("new_noise", new_noise), ("new_scale", new_scale), ("log_q_prior", log_q_prior), ("log_u", log_u)):
-            v = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
-            if v.shape[0] != self.nc:
-                raise ValueError(f"{name} has {v.shape[0]} entries for {self.nc} chains")
-            vecs.append(_lib.to_device(v))
+        vecs = [_lib.to_device(v) for v in _chains.noise_scale_vectors(new_noise, new_scale, log_q_prior, log_u, self.nc)]
         pf = packed_forest(nodes, ft)
         state = _lib.to_device(np.ascontiguousarray(np.stack([self.quad, self.logdet], axis=1)))
         accept = torch.empty(self.nc, dtype=torch.int32, device=self.K_inv.device)
@@ -552,10 +493,7 @@ class ChainBatch:
                                                         pf.info_ref, _lib.ptr(Xd), Xd.shape[1], _lib.ptr(self.y),
                                                         *(_lib.ptr(v) for v in vecs), _lib.ptr(state), _lib.ptr(accept),
                                                         _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
-        acc = accept.cpu().numpy()  # the one synchronisation of the call
-        st = state.cpu().numpy()
-        # as in sweep_trees: K_inv of the accepted chains is already rewritten, so take their state before raising
-        self.quad, self.logdet = st[:, 0].copy(), st[:, 1].copy()
+        acc, self.quad, self.logdet = _chains.read_decisions(accept, state)
         self._pending = None
         if (acc == -2).any():
             _lib.check_categorical_fault()  # reads and clears the context's flag, whatever feat_types says, and raises

@@ -17,6 +17,7 @@ import numpy as np
 
 from .. import _lib
 from ..forest import _as_nodes, _feat_types, _points, _raise_on_categorical_fault, packed_forest
+from . import _chains
 
 
 class LeafChainPlan(ctypes.Structure):
@@ -37,19 +38,6 @@ def leafchain_plan(N: int, capacity: int, m: int, lcap: int, *, nc: int = 1, d: 
     out = {name: int(getattr(plan, name)) for name, _ in LeafChainPlan._fields_}
     out["reason"] = "" if rc == 0 else lib.bark_last_error().decode(errors="replace")
     return out
-
-
-def _leaf_counts(trees, ft) -> np.ndarray:
-    """Leaves of every tree of `trees` (..., node_limit), in the packer's sense (reachable from the root)."""
-    lib = _lib.lib()
-    flat = trees.reshape(-1, trees.shape[-1])
-    out = np.empty(flat.shape[0], dtype=np.int64)
-    info = _lib.PackInfo()
-    for k in range(flat.shape[0]):
-        _lib.check(lib.bark_forest_pack_info(_lib.ptr(np.ascontiguousarray(flat[k])), 1, 1, flat.shape[1], _lib.ptr(ft), ft.shape[0],
-                                             ctypes.byref(info)))
-        out[k] = info.max_bits
-    return out.reshape(trees.shape[:-1])
 
 
 class LeafChainBatch:
@@ -89,7 +77,7 @@ class LeafChainBatch:
             raise ValueError(f"1 to {limits['max_chains']} chains")
         if self.m > limits["max_trees"]:
             raise ValueError(f"LeafChainBatch supports at most {limits['max_trees']} trees (got {self.m})")
-        self.nleaves = _leaf_counts(nodes, ft).astype(np.int32)  # host mirror of the device's leaf counts
+        self.nleaves = _chains.leaf_counts(nodes, ft).astype(np.int32)  # host mirror of the device's leaf counts
         if int(self.nleaves.max()) > self.lcap:
             raise ValueError(f"a tree has {int(self.nleaves.max())} leaves, lcap is {self.lcap}")
         total = int(self.nleaves.sum(axis=1).max())
@@ -105,12 +93,9 @@ class LeafChainBatch:
         self._ws = torch.empty(plan["workspace_bytes"], dtype=torch.uint8, device=dev)
         self._mstate = torch.empty((self.nc, 2), dtype=torch.float64, device=dev)
         pf = packed_forest(nodes, ft)
-        vecs = []
-        for name, v in (("noise", noise), ("scale", scale)):
-            vecs.append(np.broadcast_to(np.asarray(v, dtype=np.float64).reshape(-1), (self.nc,)).copy())
-        self.noise, self.scale = vecs[0].copy(), vecs[1].copy()
+        self.noise, self.scale = (_chains.broadcast_scale(v, self.nc).copy() for v in (noise, scale))
         info = torch.empty(self.nc, dtype=torch.int32, device=dev)
-        nl_d, noise_d, scale_d = _lib.to_device(self.nleaves), _lib.to_device(vecs[0]), _lib.to_device(vecs[1])  # alive until the read-back
+        nl_d, noise_d, scale_d = _lib.to_device(self.nleaves), _lib.to_device(self.noise), _lib.to_device(self.scale)  # alive until the read-back
         _lib.check(lib.bark_leafchain_init_hip(_lib.ctx(), _lib.ptr(self.state), *self._shape(), _lib.ptr(pf.packed), pf.info_ref,
                                                _lib.ptr(nl_d), _lib.ptr(Xd), Xd.shape[1], _lib.ptr(self.y),
                                                _lib.ptr(noise_d), _lib.ptr(scale_d),
@@ -144,64 +129,36 @@ class LeafChainBatch:
         """The query for this batch's shape (`leafchain_plan`)."""
         return dict(self.plan)
 
-    def _points_of(self, X, ft):
-        if self._X_seen is None or self._X_seen[0] is not X:
-            Xd, _ = _points(X, ft.shape[0])
-            self._X_seen = (X, Xd)
-        Xd = self._X_seen[1]
-        if Xd.shape[0] != self.N:
-            raise ValueError(f"X has {Xd.shape[0]} rows, the chains have {self.N} points")
-        return Xd
-
     def _prepare_sweep(self, old_trees, new_trees, log_q_prior, log_u, X, feat_types, scale, m, tree_index):
         """Validate, pack and upload a sweep -> (enqueue, accept tensor, tree indices, r_new, feat_types)."""
-        import torch
-
         lib = _lib.lib()
         ft = _feat_types(feat_types)
-        Xd = self._points_of(X, ft)
-        old, new = _as_nodes(old_trees, 3), _as_nodes(new_trees, 3)
-        if old.shape != new.shape or old.ndim != 3 or old.shape[0] != self.nc:
-            raise ValueError(f"trees must be (chains, steps, node_limit) records, got {old.shape} and {new.shape}")
+        Xd = _chains.points_of(self, X, ft, "chains have")
+        old, new = _chains.check_step_trees(old_trees, new_trees, self.nc)
         steps = old.shape[1]
         if int(m) != self.m:
             raise ValueError(f"m = {m}, the chains have {self.m} trees")
-        scale = np.broadcast_to(np.asarray(scale, dtype=np.float64).reshape(-1), (self.nc,))
-        if not np.array_equal(scale, self.scale):
+        if not np.array_equal(_chains.broadcast_scale(scale, self.nc), self.scale):
             raise ValueError("scale differs from the chains' own (step_noise_scale changes it)")
         tidx = np.arange(steps, dtype=np.int64) if tree_index is None else np.ascontiguousarray(tree_index, dtype=np.int64).reshape(-1)
         if tidx.shape[0] != steps or (tidx < 0).any() or (tidx >= self.m).any():
             raise ValueError(f"tree_index must hold {steps} indices in 0..{self.m - 1}")
-        lq = np.ascontiguousarray(np.asarray(log_q_prior, dtype=np.float64).reshape(self.nc, steps).T)  # (steps, chains)
-        lu = np.ascontiguousarray(np.asarray(log_u, dtype=np.float64).reshape(self.nc, steps).T)
-        r_old = _leaf_counts(old, ft)
+        lq, lu = _chains.steps_major(log_q_prior, self.nc, steps), _chains.steps_major(log_u, self.nc, steps)
+        r_old = _chains.leaf_counts(old, ft)
         first = {}
         for t in range(steps):
             first.setdefault(int(tidx[t]), t)
         for k, t in first.items():
             if not np.array_equal(r_old[:, t], self.nleaves[:, k]):
                 raise ValueError(f"old_trees[:, {t}] is not tree {k} of the chains (leaf counts {r_old[:, t]} against {self.nleaves[:, k]})")
-        r_new = np.ascontiguousarray(_leaf_counts(new, ft).T)  # (steps, chains)
-        infos = (_lib.PackInfo * steps)()
-        sizes, singles = [], []
-        for t in range(steps):
-            one = np.ascontiguousarray(new[:, t][:, None])  # (chains, 1, L)
-            singles.append(one)
-            _lib.check(lib.bark_forest_pack_info(_lib.ptr(one), self.nc, 1, one.shape[2], _lib.ptr(ft), ft.shape[0], ctypes.byref(infos[t])))
-            sizes.append(int(infos[t].packed_bytes))
-        offsets = np.zeros(steps, dtype=np.int64)
-        offsets[1:] = np.cumsum([(sz + 255) // 256 * 256 for sz in sizes[:-1]])
+        r_new = np.ascontiguousarray(_chains.leaf_counts(new, ft).T)  # (steps, chains)
+        infos, offsets, _, host = _chains.pack_steps_host([new[:, t][:, None] for t in range(steps)], ft)
         table = np.empty(int(lib.bark_leafchain_sweep_table_bytes(steps, self.nc)) // 8, dtype=np.int64)
         _lib.check(lib.bark_leafchain_sweep_table(_lib.ptr(offsets), ctypes.cast(infos, ctypes.c_void_p), _lib.ptr(tidx), _lib.ptr(r_new),
                                                   _lib.ptr(np.ascontiguousarray(self.nleaves)), steps, self.nc, self.m, self.lcap,
                                                   self.capacity, _lib.ptr(table)))
-        host = torch.empty(int(offsets[-1]) + sizes[-1], dtype=torch.uint8)
-        for t in range(steps):
-            _lib.check(lib.bark_forest_pack(_lib.ptr(singles[t]), _lib.ptr(ft), ft.shape[0], ctypes.byref(infos[t]),
-                                            ctypes.c_void_p(host.data_ptr() + int(offsets[t]))))
-        packed, table_d = host.to(self.state.device), _lib.to_device(table)
-        lq_d, lu_d = _lib.to_device(lq), _lib.to_device(lu)
-        accept = torch.empty((steps, self.nc), dtype=torch.int32, device=self.state.device)
+        packed, lq_d, lu_d, accept = _chains.upload_sweep(host, lq, lu)
+        table_d = _lib.to_device(table)
         shape = self._shape()
 
         def enqueue():  # only enqueues: capturable in a graph; the closure keeps the step's device buffers alive
@@ -226,11 +183,8 @@ class LeafChainBatch:
         return self._finish_sweep(accept, tidx, r_new, ft)
 
     def _finish_sweep(self, accept, tidx, r_new, ft) -> np.ndarray:
-        steps = accept.shape[0]
-        acc = accept.cpu().numpy()  # the one synchronisation of the sweep
-        # the device has already rewritten P for every accepted step: take the state that belongs to it BEFORE raising
-        self._take_state()
-        for t in range(steps):
+        acc, self.quad, self.logdet = _chains.read_decisions(accept, self._mstate)
+        for t in range(acc.shape[0]):
             took = acc[t] > 0
             self.nleaves[took, tidx[t]] = r_new[t, took]
         self.last_accept = acc.T.copy()
@@ -245,19 +199,13 @@ class LeafChainBatch:
         noise and scale of its chains itself (`.noise`, `.scale`)."""
         import torch
 
-        vecs = []
-        for name, v in (("new_noise", new_noise), ("new_scale", new_scale), ("log_q_prior", log_q_prior), ("log_u", log_u)):
-            v = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
-            if v.shape[0] != self.nc:
-                raise ValueError(f"{name} has {v.shape[0]} entries for {self.nc} chains")
-            vecs.append(v)
+        vecs = _chains.noise_scale_vectors(new_noise, new_scale, log_q_prior, log_u, self.nc)
         dev = [_lib.to_device(v) for v in vecs]
         accept = torch.empty(self.nc, dtype=torch.int32, device=self.state.device)
         _lib.check(_lib.lib().bark_leafchain_noise_scale_hip(_lib.ctx(), _lib.ptr(self.state), *self._shape(), *(_lib.ptr(v) for v in dev),
                                                              _lib.ptr(self._mstate), _lib.ptr(accept), _lib.ptr(self._ws),
                                                              self._ws.numel(), _lib.stream_ptr()))
-        acc = accept.cpu().numpy()  # the one synchronisation of the call
-        self._take_state()
+        acc, self.quad, self.logdet = _chains.read_decisions(accept, self._mstate)
         took = acc > 0
         self.noise, self.scale = np.where(took, vecs[0], self.noise), np.where(took, vecs[1], self.scale)
         if (acc < 0).any():
