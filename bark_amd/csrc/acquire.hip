@@ -273,18 +273,28 @@ size_t scan_lds_bytes(int64_t R, int64_t m, bool lds_table) {
     return (lds_table ? ((size_t)R * (R + 1) / 2 + R) * sizeof(double) : 0) + lists;
 }
 
+size_t acq_condition_lds_bytes(int64_t R) { return ((size_t)R + 1) * sizeof(double) + (ACQ_MAX_TREES + 2) * sizeof(int); }
+
+// The two kernels of this unit that can use more than 64 KiB of dynamic LDS: the LDS variant of the scan (up to a whole CU's)
+// and acq_condition_kernel at the largest R the leaf-space path admits (8192: 264 bytes past 64 KiB).  acq_condition and
+// acq_scan call this before they launch.
+int raise_acq_lds_limits() {
+    static const LdsLimit limits[] = {{reinterpret_cast<const void *>(acq_scan_kernel<true>), ACQ_LDS_MAX},
+                                      {reinterpret_cast<const void *>(acq_condition_kernel), acq_condition_lds_bytes(8192)}};
+    static LdsLimitsOnce once;
+    return raise_lds_limits(once, limits);
+}
+
 }  // namespace
 
-const void *acq_scan_lds_kernel_ptr() { return reinterpret_cast<const void *>(acq_scan_kernel<true>); }
-size_t acq_lds_max() { return ACQ_LDS_MAX; }
-const void *acq_condition_kernel_ptr() { return reinterpret_cast<const void *>(acq_condition_kernel); }
-size_t acq_condition_lds_bytes(int64_t R) { return ((size_t)R + 1) * sizeof(double) + (ACQ_MAX_TREES + 2) * sizeof(int); }
 int64_t acq_partials(int64_t C) { return (C + 255) / 256; }
 size_t acq_table_doubles(int64_t R) { return (size_t)R * (R + 1) / 2 + R; }
 
 // M^-1 of the chunk's forests conditioned on the P pending points whose codes are pcodes (bc, W, ppad)
 int acq_condition(const uint32_t *pcodes, int W, int ppad, int P, double *Minv, int R, const double *noise, const double *scale,
                   int m, int bc, const int32_t *info, hipStream_t s) {
+    const int rc = raise_acq_lds_limits();
+    if (rc) return rc;
     hipLaunchKernelGGL(acq_condition_kernel, dim3((unsigned)bc), dim3(ACQ_COND_THREADS), acq_condition_lds_bytes(R), s, pcodes, W,
                        ppad, P, Minv, R, noise, scale, m, info);
     BARK_LAUNCH_CHECK();
@@ -303,6 +313,8 @@ int acq_scan(int variant, const uint32_t *ccodes, int W, int cpad, int n, const 
              const double *tab, int R, const double *noise, const double *scale, int m, int bc, double kappa, int first,
              double *acc, size_t astride, hipStream_t s) {
     const dim3 g((unsigned)((n + ACQ_TILE - 1) / ACQ_TILE));
+    const int rc = raise_acq_lds_limits();
+    if (rc) return rc;
     if (variant == 1)
         hipLaunchKernelGGL(acq_scan_kernel<true>, g, dim3(ACQ_TILE), scan_lds_bytes(R, m, true), s, ccodes, W, cpad, n, wvec, Minv,
                            tab, R, noise, scale, m, bc, kappa, first, acc, astride);

@@ -54,62 +54,11 @@
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
-#include <mutex>
 #include <optional>
 #include <type_traits>
 #include <vector>
 
 #include "common.h"
-
-namespace bark {
-
-int walk_one_hot(const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d, int words,
-                 uint32_t *out, int32_t *fault, hipStream_t stream);
-int walk_codes(const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d, uint32_t *out,
-               int32_t *fault, hipStream_t stream);
-int leafspace_prepare(const uint32_t *codes, int W, int npad, unsigned long long *planes, int R, int Rpad,
-                      const double *noise, const double *scale, int m, int bc, double *A, long ld, long bstride,
-                      const double *y, int N, double *yz, double *accum, int32_t *info, hipStream_t s);
-int leafspace_sumsq(const double *y, int N, double *out, hipStream_t s);
-int leafspace_predict(const uint32_t *ccodes, int W, int cpad, int C, const double *w, const double *Minv, int R,
-                      const double *noise, const double *scale, int m, int bc, double *mu, double *var, hipStream_t s);
-int leafspace_inverse(const uint32_t *codes, int W, int npad, int N, const double *Minv, const double *w, int R,
-                      const double *y, const double *noise, const double *scale, int m, int bc, double *Wm, double *kinv,
-                      double *kinv_y, const int32_t *accept, hipStream_t s);
-int noise_scale_decide(const double *new_mll, const double *state, const double *noise, const double *log_q_prior,
-                       const double *log_u, const int32_t *info, const int32_t *fault, int nc, int32_t *accept_out,
-                       hipStream_t s);
-int noise_scale_state(const double *kinv_y, const double *y, int N, const double *new_mll, const int32_t *accept, int nc,
-                      double *state, hipStream_t s);
-int leafspace_finish(const double *accum, const double *yy, const double *noise, const double *scale, int m, int bc, int N,
-                     int include_2pi, double *mll, hipStream_t s);
-int acq_pack(const double *Minv, const double *w, int R, int bc, double *tab, hipStream_t s);
-int acq_scan(int variant, const uint32_t *ccodes, int W, int cpad, int n, const double *wvec, const double *Minv,
-             const double *tab, int R, const double *noise, const double *scale, int m, int bc, double kappa, int first,
-             double *acc, size_t astride, hipStream_t s);
-int acq_condition(const uint32_t *pcodes, int W, int ppad, int P, double *Minv, int R, const double *noise, const double *scale,
-                  int m, int bc, const int32_t *info, hipStream_t s);
-int acq_finish(const double *acc, int64_t C, int B, double kappa, int kind, const int64_t *skip, int n_skip, double *acq_out,
-               double *part_v, int64_t *part_i,
-               const int32_t *info, double *best, int64_t *best_i, hipStream_t s);
-const void *acq_scan_lds_kernel_ptr();
-const void *acq_condition_kernel_ptr();
-size_t acq_condition_lds_bytes(int64_t R);
-size_t acq_lds_max();
-int64_t acq_partials(int64_t C);
-size_t acq_table_doubles(int64_t R);
-int64_t sample_spad(int64_t S);
-int64_t sample_partials(int64_t C, int64_t S);
-int sample_weights(const double *V, long ldv, long vstride, const double *w, const double *eps, int R, int Rpad, int S,
-                   int Spad, const double *noise, const double *scale, int m, int bc, double *Wt, hipStream_t s);
-int sample_gather(const uint32_t *ccodes, int W, int cpad, int C, const double *Wt, int Rpad, int Spad, int S, int m, int bc,
-                  int reduce, double *f, double *red, int64_t *ridx, double *part, int64_t *part_i, hipStream_t s);
-
-int launch_gram(const uint32_t *leaf1, int npad1, const uint32_t *leaf2, int npad2, int64_t B, int64_t m, int N, int M,
-                int Nout, int Mout, const double *shift, const double *scale, const double *noise, double *out, int64_t ld,
-                int64_t batch_stride, bool pad_identity, bool upper_only, int rep, int words, hipStream_t stream);
-
-}  // namespace bark
 
 #include "chol_solve.h"  // -> chol_rows.h -> chol_diag.h -> chol_tiles.h
 
@@ -349,50 +298,35 @@ static_assert(DIAG_LDS >= GEMM_LDS, "diag kernel reuses its LDS for the K=128 GE
 // pattern is fork/join, so it is capturable.
 // (Tried and rejected: splitting the resident matrices into two independently advancing lanes so that
 // one lane's panel kernel covers the other's diag/solve phases — 5 % slower at B = 256, 4 % at B = 64.)
-}  // namespace
 
+// The kernels of this unit that use more than 64 KiB of dynamic LDS (common.h: raise_lds_limits).  Everything that runs a
+// Sweep calls this before its first launch: bark_mll_batched_hip and LeafSystem::open.
 int set_lds_limits() {
-    // kernels using more than 64 KiB of dynamic LDS need the limit raised once per device
-    static std::once_flag once[64];
-    static int status[64];
-    int dev = 0;
-    BARK_HIP_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return fail(BARK_ERR_ARG, "device index %d out of range", dev);
-    std::call_once(once[dev], [dev]() {
-        auto set = [](const void *fn, size_t bytes) {
-            return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-        };
-        hipError_t e = set(reinterpret_cast<const void *>(diag_kernel<false, 4>), DIAG_LDS_EXCLUSIVE);
-        if (e == hipSuccess) e = set(reinterpret_cast<const void *>(diag_kernel<true, 4>), DIAG_LDS_EXCLUSIVE);
-        if (e == hipSuccess) e = set(reinterpret_cast<const void *>(multi_block_kernel), DIAG_LDS_EXCLUSIVE);
-        if (e == hipSuccess) e = set(reinterpret_cast<const void *>(two_block_kernel<4>), DIAG_LDS_EXCLUSIVE);
-        if (e == hipSuccess) e = set(reinterpret_cast<const void *>(two_block_kernel<8>), DIAG_LDS_EXCLUSIVE);
-        if (e == hipSuccess) e = set(reinterpret_cast<const void *>(diag_kernel<false, 8>), DIAG_LDS_EXCLUSIVE);
-        if (e == hipSuccess) e = set(reinterpret_cast<const void *>(diag_kernel<true, 8>), DIAG_LDS_EXCLUSIVE);
-        if (e == hipSuccess) e = set(reinterpret_cast<const void *>(row_kernel<0>), GEMM_LDS);
-        if (e == hipSuccess) e = set(reinterpret_cast<const void *>(row_kernel<1>), GEMM_LDS);
-        if (e == hipSuccess) e = set(reinterpret_cast<const void *>(row_kernel<2>), GEMM_LDS);
-        if (e == hipSuccess) e = set(reinterpret_cast<const void *>(row_kernel<3>), GEMM_LDS);
-        if (e == hipSuccess) e = set(reinterpret_cast<const void *>(panel_split_kernel), GEMM_LDS);
-        if (e == hipSuccess) e = set(reinterpret_cast<const void *>(vtv_kernel), GEMM_LDS);
-        if (e == hipSuccess) e = set(reinterpret_cast<const void *>(solve_kernel<0>), GEMM_LDS);
-        if (e == hipSuccess) e = set(reinterpret_cast<const void *>(solve_kernel<1>), GEMM_LDS);
-        if (e == hipSuccess) e = set(reinterpret_cast<const void *>(solve_narrow_kernel<1>), GEMM_LDS);
-        if (e == hipSuccess) e = set(reinterpret_cast<const void *>(solve_narrow_kernel<2>), GEMM_LDS);
-        if (e == hipSuccess) e = set(reinterpret_cast<const void *>(solve_narrow_kernel<1, 1>), GEMM_LDS);
-        if (e == hipSuccess) e = set(reinterpret_cast<const void *>(solve_narrow_kernel<2, 1>), GEMM_LDS);
-        if (e == hipSuccess) e = set(leaf_inverse_kernel_ptr(), LEAF_INV_LDS_MAX);
-        if (e == hipSuccess) e = set(acq_scan_lds_kernel_ptr(), acq_lds_max());
-        if (e == hipSuccess) e = set(acq_condition_kernel_ptr(), acq_condition_lds_bytes(8192));
-        status[dev] = (int)e;
-    });
-    if (status[dev] != 0)
-        return fail(BARK_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s",
-                    hipGetErrorString((hipError_t)status[dev]));
-    return BARK_OK;
+    auto fn = [](auto *kernel) { return reinterpret_cast<const void *>(kernel); };
+    static const LdsLimit table[] = {
+        {fn(diag_kernel<false, 4>), DIAG_LDS_EXCLUSIVE},
+        {fn(diag_kernel<true, 4>), DIAG_LDS_EXCLUSIVE},
+        {fn(multi_block_kernel), DIAG_LDS_EXCLUSIVE},
+        {fn(two_block_kernel<4>), DIAG_LDS_EXCLUSIVE},
+        {fn(two_block_kernel<8>), DIAG_LDS_EXCLUSIVE},
+        {fn(diag_kernel<false, 8>), DIAG_LDS_EXCLUSIVE},
+        {fn(diag_kernel<true, 8>), DIAG_LDS_EXCLUSIVE},
+        {fn(row_kernel<0>), GEMM_LDS},
+        {fn(row_kernel<1>), GEMM_LDS},
+        {fn(row_kernel<2>), GEMM_LDS},
+        {fn(row_kernel<3>), GEMM_LDS},
+        {fn(panel_split_kernel), GEMM_LDS},
+        {fn(vtv_kernel), GEMM_LDS},
+        {fn(solve_kernel<0>), GEMM_LDS},
+        {fn(solve_kernel<1>), GEMM_LDS},
+        {fn(solve_narrow_kernel<1>), GEMM_LDS},
+        {fn(solve_narrow_kernel<2>), GEMM_LDS},
+        {fn(solve_narrow_kernel<1, 1>), GEMM_LDS},
+        {fn(solve_narrow_kernel<2, 1>), GEMM_LDS},
+    };
+    static LdsLimitsOnce once;
+    return raise_lds_limits(once, table);
 }
-
-namespace {
 
 // ---------------------------------------------------------------------------------------------
 // The shape of a sweep, and the rules that depend on nothing but the shape, the chunk size bc and the block step j: Sweep

@@ -5,6 +5,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <mutex>
 #include <vector>
 
 #include "../../include/bark_hip.h"
@@ -55,17 +56,93 @@ struct bark_ctx {
 
 namespace bark {
 
+// ---------------------------------------------------------------------------------------------------------------
+// Host functions that one translation unit defines and another calls: declared here and nowhere else, so the defining
+// unit compiles against the declaration its callers use.
+// ---------------------------------------------------------------------------------------------------------------
+// ctx.hip
 // ctx valid and made for the current device?  (entry points call this first)
 int check_ctx(const bark_ctx *ctx);
 int ctx_events(bark_ctx *ctx, size_t n);          // at least n events in ctx->events
 int ctx_chain_streams(bark_ctx *ctx, size_t n);   // at least n chain streams + events
-int set_lds_limits();                             // once per device: kernels with > 64 KiB of dynamic LDS (chol.hip)
 
-// leaf-space inverse (leafspace.hip): leaf_inverse_kernel keeps the leaf lists of its 64 columns in dynamic LDS, m x 64
-// 16-bit ids, so it takes forests of at most 160 KiB / 128 B = 1280 trees
+// A kernel that uses more than 64 KiB of dynamic LDS needs its limit raised once per device.  Every unit owns the table of
+// its own kernels (and the once-per-device state that goes with it) and calls raise_lds_limits from its launch path, before
+// the first launch that can need it; never from a query or a *_workspace_bytes function, which run without a device.
+struct LdsLimit {
+    const void *kernel;
+    size_t bytes;
+};
+struct LdsLimitsOnce {
+    std::once_flag once[64];
+    int status[64] = {};
+};
+// checked; safe from several host threads; a current device outside 0..63 is refused
+int raise_lds_limits(LdsLimitsOnce &state, const LdsLimit *table, size_t count);
+template <size_t COUNT>
+int raise_lds_limits(LdsLimitsOnce &state, const LdsLimit (&table)[COUNT]) {
+    return raise_lds_limits(state, table, COUNT);
+}
+
+// traverse.hip
+// one-hot leaf code with `words` = ceil(max_bits / 32) planes, whatever encoding the Gram kernels would pick
+int walk_one_hot(const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d, int words,
+                 uint32_t *out, int32_t *fault, hipStream_t stream);
+// Gram-kernel leaf codes (encoding chosen from `info`), for the sweep entry points that already hold a context
+int walk_codes(const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d, uint32_t *out,
+               int32_t *fault, hipStream_t stream);
+
+// gram.hip (the MLL engine fills its workspace with this kernel)
+int launch_gram(const uint32_t *leaf1, int npad1, const uint32_t *leaf2, int npad2, int64_t B, int64_t m, int N, int M,
+                int Nout, int Mout, const double *shift, const double *scale, const double *noise, double *out, int64_t ld,
+                int64_t batch_stride, bool pad_identity, bool upper_only, int rep, int words, hipStream_t stream);
+
+// leafspace.hip: launchers of the leaf-space entry points (LeafSystem, chol.hip)
+// leaf_inverse_kernel keeps the leaf lists of its 64 columns in dynamic LDS, m x 64 16-bit ids, so it takes forests of at
+// most 160 KiB / 128 B = 1280 trees
 constexpr int LEAF_INV_MAX_TREES = 1280;
-constexpr size_t LEAF_INV_LDS_MAX = (size_t)LEAF_INV_MAX_TREES * 64 * sizeof(unsigned short);
-const void *leaf_inverse_kernel_ptr();            // for set_lds_limits
+int leafspace_prepare(const uint32_t *codes, int W, int npad, unsigned long long *planes, int R, int Rpad,
+                      const double *noise, const double *scale, int m, int bc, double *A, long ld, long bstride,
+                      const double *y, int N, double *yz, double *accum, int32_t *info, hipStream_t s);
+int leafspace_sumsq(const double *y, int N, double *out, hipStream_t s);
+int leafspace_predict(const uint32_t *ccodes, int W, int cpad, int C, const double *w, const double *Minv, int R,
+                      const double *noise, const double *scale, int m, int bc, double *mu, double *var, hipStream_t s);
+int leafspace_inverse(const uint32_t *codes, int W, int npad, int N, const double *Minv, const double *w, int R,
+                      const double *y, const double *noise, const double *scale, int m, int bc, double *Wm, double *kinv,
+                      double *kinv_y, const int32_t *accept, hipStream_t s);
+int leafspace_finish(const double *accum, const double *yy, const double *noise, const double *scale, int m, int bc, int N,
+                     int include_2pi, double *mll, hipStream_t s);
+int noise_scale_decide(const double *new_mll, const double *state, const double *noise, const double *log_q_prior,
+                       const double *log_u, const int32_t *info, const int32_t *fault, int nc, int32_t *accept_out,
+                       hipStream_t s);
+int noise_scale_state(const double *kinv_y, const double *y, int N, const double *new_mll, const int32_t *accept, int nc,
+                      double *state, hipStream_t s);
+
+// sample.hip
+int64_t sample_spad(int64_t S);                    // padded Wt row: a multiple of the draws per gather pass
+int64_t sample_partials(int64_t C, int64_t S);
+// Wt (bc, Rpad, Spad) from V (leading dimension ldv, matrix stride vstride), w (bc, R) and eps (bc, S, R)
+int sample_weights(const double *V, long ldv, long vstride, const double *w, const double *eps, int R, int Rpad, int S,
+                   int Spad, const double *noise, const double *scale, int m, int bc, double *Wt, hipStream_t s);
+// f (bc, S, C) for reduce == BARK_SAMPLE_FULL; otherwise red / ridx (bc, S) through `part` (sample_partials(C, S) x bc
+// doubles) and `part_i` (as many int64)
+int sample_gather(const uint32_t *ccodes, int W, int cpad, int C, const double *Wt, int Rpad, int Spad, int S, int m, int bc,
+                  int reduce, double *f, double *red, int64_t *ridx, double *part, int64_t *part_i, hipStream_t s);
+
+// acquire.hip
+int64_t acq_partials(int64_t C);
+size_t acq_table_doubles(int64_t R);
+// M^-1 of the chunk's forests conditioned on the P pending points whose codes are pcodes (bc, W, ppad)
+int acq_condition(const uint32_t *pcodes, int W, int ppad, int P, double *Minv, int R, const double *noise, const double *scale,
+                  int m, int bc, const int32_t *info, hipStream_t s);
+// image of the chunk for the LDS variant
+int acq_pack(const double *Minv, const double *w, int R, int bc, double *tab, hipStream_t s);
+// variant: 1 LDS, 2 global (resolved by bark_acquisition_plan); n candidates of one slab against the bc forests of the chunk
+int acq_scan(int variant, const uint32_t *ccodes, int W, int cpad, int n, const double *wvec, const double *Minv,
+             const double *tab, int R, const double *noise, const double *scale, int m, int bc, double kappa, int first,
+             double *acc, size_t astride, hipStream_t s);
+int acq_finish(const double *acc, int64_t C, int B, double kappa, int kind, const int64_t *skip, int n_skip, double *acq_out,
+               double *part_v, int64_t *part_i, const int32_t *info, double *best, int64_t *best_i, hipStream_t s);
 
 constexpr size_t STAGE_BYTES = 64 * 1024;  // bark_ctx::stage_host / stage_dev
 constexpr int NODE_BYTES = 26;          // forest.py:8-19, packed

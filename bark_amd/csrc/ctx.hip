@@ -3,7 +3,8 @@
 // The reference's callers are single-threaded Python; the library is re-entrant per context: helper
 // streams, events, the scratch buffer and the categorical-fault flag belong to a bark_ctx, created and destroyed
 // explicitly.  The only process-wide state left is the thread-local last-error buffer and the once-per-device
-// dynamic-LDS attributes of the kernels (std::call_once).
+// dynamic-LDS attributes of the kernels: raise_lds_limits below sets them, from the table and the LdsLimitsOnce of the
+// translation unit that owns the kernels.
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
@@ -35,6 +36,22 @@ int check_ctx(const bark_ctx *ctx) {
     BARK_HIP_CHECK(hipGetDevice(&dev));
     if (dev != ctx->device)
         return fail(BARK_ERR_ARG, "bark_ctx belongs to device %d but the current device is %d", ctx->device, dev);
+    return BARK_OK;
+}
+
+int raise_lds_limits(LdsLimitsOnce &state, const LdsLimit *table, size_t count) {
+    int dev = 0;
+    BARK_HIP_CHECK(hipGetDevice(&dev));
+    if (dev < 0 || dev >= 64) return fail(BARK_ERR_ARG, "device index %d out of range", dev);
+    std::call_once(state.once[dev], [&]() {
+        hipError_t e = hipSuccess;
+        for (size_t i = 0; i < count && e == hipSuccess; ++i)
+            e = hipFuncSetAttribute(table[i].kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)table[i].bytes);
+        state.status[dev] = (int)e;
+    });
+    if (state.status[dev] != 0)
+        return fail(BARK_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s",
+                    hipGetErrorString((hipError_t)state.status[dev]));
     return BARK_OK;
 }
 

@@ -307,8 +307,6 @@ __global__ __launch_bounds__(64) void noise_scale_state_kernel(const double *__r
 
 }  // namespace
 
-const void *leaf_inverse_kernel_ptr() { return reinterpret_cast<const void *>(leaf_inverse_kernel); }
-
 int leafspace_predict(const uint32_t *ccodes, int W, int cpad, int C, const double *w, const double *Minv, int R,
                       const double *noise, const double *scale, int m, int bc, double *mu, double *var, hipStream_t s) {
     if (m > LP_MAX_TREES) return fail(BARK_ERR_ARG, "leaf-space posterior supports at most %d trees", LP_MAX_TREES);
@@ -323,6 +321,12 @@ int leafspace_inverse(const uint32_t *codes, int W, int npad, int N, const doubl
                       double *kinv_y, const int32_t *accept, hipStream_t s) {
     if (R > 65535 || m > LEAF_INV_MAX_TREES)
         return fail(BARK_ERR_ARG, "leaf-space inverse supports at most %d trees (got m = %d, R = %d)", LEAF_INV_MAX_TREES, m, R);
+    // leaf_inverse_kernel's leaf lists (m x 64 16-bit ids) pass 64 KiB from 513 trees on
+    static const LdsLimit limits[] = {
+        {reinterpret_cast<const void *>(leaf_inverse_kernel), (size_t)LEAF_INV_MAX_TREES * 64 * sizeof(unsigned short)}};
+    static LdsLimitsOnce once;
+    const int rc = raise_lds_limits(once, limits);
+    if (rc) return rc;
     hipLaunchKernelGGL(leaf_rowsum_kernel, dim3((unsigned)((N + 3) / 4), (unsigned)bc), dim3(256), 0, s, codes, W, npad, N, Minv,
                        w, R, y, noise, scale, m, Wm, kinv_y, accept);
     BARK_LAUNCH_CHECK();

@@ -18,9 +18,6 @@
 #include "common.h"
 
 namespace bark {
-int walk_one_hot(const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d, int words,
-                 uint32_t *out, int32_t *fault, hipStream_t stream);  // traverse.hip
-
 namespace {
 
 constexpr int LR_MAX = 64;  // max rank r
@@ -579,35 +576,64 @@ struct SkinnyCfg {
     static constexpr int KL = RT <= 16 ? SK_KL_SMALL : 1;
 };
 
+// dynamic LDS of skinny_kernel<RT, ...> at rank r: the double-buffered, padded U chunk (130 KiB at r = 64)
+template <int RT>
+constexpr size_t skinny_lds_bytes(int r) {
+    return (size_t)2 * (128 * SkinnyCfg<RT>::KL + 2) * r * sizeof(double);
+}
+
+// The skinny_kernel instantiations whose dynamic LDS passes 64 KiB at the top rank of their bound (r = RT), each at that
+// maximum: with KL = 1 the bounds 32 (from r = 32) and 64.  Derived from SkinnyCfg, so a build with another SK_KL_SMALL stays right.
+struct SkinnyLimits {
+    LdsLimit table[8];
+    size_t count = 0;
+    template <int RT>
+    void add() {
+        constexpr int RW = SkinnyCfg<RT>::RW, KL = SkinnyCfg<RT>::KL;
+        if constexpr (skinny_lds_bytes<RT>(RT) > 64 * 1024) {
+            table[count++] = {reinterpret_cast<const void *>(skinny_kernel<RT, true, RW, KL>), skinny_lds_bytes<RT>(RT)};
+            table[count++] = {reinterpret_cast<const void *>(skinny_kernel<RT, false, RW, KL>), skinny_lds_bytes<RT>(RT)};
+        }
+    }
+    SkinnyLimits() {
+        add<8>();
+        add<16>();
+        add<32>();
+        add<64>();
+    }
+};
+
 template <int RT>
 int launch_skinny_rt(hipStream_t stream, const double *K, const double *U, int N, int r, double *out, const double *y,
                      double *partial) {
     constexpr int RW = SkinnyCfg<RT>::RW, KL = SkinnyCfg<RT>::KL, ROWS = 4 * RW;
     const dim3 grid((unsigned)((N + ROWS - 1) / ROWS));
-    const size_t lds = (size_t)2 * (128 * KL + 2) * r * sizeof(double);  // 130 KiB at r = 64
-    if (N % 2 == 0) {
-        if (lds > 64 * 1024)
-            (void)hipFuncSetAttribute((const void *)skinny_kernel<RT, true, RW, KL>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const size_t lds = skinny_lds_bytes<RT>(r);
+    if (N % 2 == 0)
         hipLaunchKernelGGL((skinny_kernel<RT, true, RW, KL>), grid, dim3(LR_THREADS), lds, stream, K, U, N, r, out, y,
                            partial);
-    } else {
-        if (lds > 64 * 1024)
-            (void)hipFuncSetAttribute((const void *)skinny_kernel<RT, false, RW, KL>,
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    else
         hipLaunchKernelGGL((skinny_kernel<RT, false, RW, KL>), grid, dim3(LR_THREADS), lds, stream, K, U, N, r, out, y,
                            partial);
-    }
     return (int)grid.x;
 }
 
-// returns the number of workgroups (= shares written to `partial`)
+// -> *nblocks = the number of workgroups (= shares written to `partial`)
 int launch_skinny(hipStream_t stream, const double *K, const double *U, int N, int r, double *out, const double *y,
-                  double *partial) {
-    if (r <= 8) return launch_skinny_rt<8>(stream, K, U, N, r, out, y, partial);
-    if (r <= 16) return launch_skinny_rt<16>(stream, K, U, N, r, out, y, partial);
-    if (r <= 32) return launch_skinny_rt<32>(stream, K, U, N, r, out, y, partial);
-    return launch_skinny_rt<64>(stream, K, U, N, r, out, y, partial);
+                  double *partial, int *nblocks) {
+    static const SkinnyLimits limits;
+    static LdsLimitsOnce once;
+    const int rc = raise_lds_limits(once, limits.table, limits.count);
+    if (rc) return rc;
+    if (r <= 8)
+        *nblocks = launch_skinny_rt<8>(stream, K, U, N, r, out, y, partial);
+    else if (r <= 16)
+        *nblocks = launch_skinny_rt<16>(stream, K, U, N, r, out, y, partial);
+    else if (r <= 32)
+        *nblocks = launch_skinny_rt<32>(stream, K, U, N, r, out, y, partial);
+    else
+        *nblocks = launch_skinny_rt<64>(stream, K, U, N, r, out, y, partial);
+    return BARK_OK;
 }
 
 // Column form K'U (== K U for symmetric K): usable when N is even and r <= 16.  `partial` may be null (no shares).
@@ -768,9 +794,11 @@ int bark_lowrank_update_hip(const double *K_inv, int64_t N, const double *U, int
     const LowRankWs w = lowrank_ws(workspace, N, r);
     const int r_neg = subtract ? (int)r : 0;
     const bool colform = colsum_usable(N, r);
-    const int nblocks = (symmetric && colform)
-                            ? launch_colsum(stream, K_inv, U, (int)N, (int)r, w.P, w.Y, nullptr, w.partial)
-                            : launch_skinny(stream, K_inv, U, (int)N, (int)r, w.Y, nullptr, w.partial);
+    int nblocks = 0, rc = BARK_OK;
+    if (symmetric && colform)
+        nblocks = launch_colsum(stream, K_inv, U, (int)N, (int)r, w.P, w.Y, nullptr, w.partial);
+    else if ((rc = launch_skinny(stream, K_inv, U, (int)N, (int)r, w.Y, nullptr, w.partial, &nblocks)))
+        return rc;
     BARK_LAUNCH_CHECK();
     const double *Rp = w.Y;
     if (K_out && !symmetric) {  // right factor U' K_inv as its own pass
@@ -825,8 +853,11 @@ int bark_lowrank_swap_eval_hip(const double *K_inv, int64_t N, const double *U, 
     if (workspace_bytes < bark_lowrank_workspace_bytes(N, r)) return fail(BARK_ERR_WORKSPACE, "low-rank workspace too small");
     hipStream_t stream = static_cast<hipStream_t>(stream_);
     const LowRankWs w = lowrank_ws(workspace, N, r);
-    const int nblocks = colsum_usable(N, r) ? launch_colsum(stream, K_inv, U, (int)N, (int)r, w.P, w.Y, y, w.partial)
-                                            : launch_skinny(stream, K_inv, U, (int)N, (int)r, w.Y, y, w.partial);
+    int nblocks = 0, rc = BARK_OK;
+    if (colsum_usable(N, r))
+        nblocks = launch_colsum(stream, K_inv, U, (int)N, (int)r, w.P, w.Y, y, w.partial);
+    else if ((rc = launch_skinny(stream, K_inv, U, (int)N, (int)r, w.Y, y, w.partial, &nblocks)))
+        return rc;
     BARK_LAUNCH_CHECK();
     BARK_HIP_CHECK(hipMemsetAsync(w.flag, 0, sizeof(int), stream));
     launch_small(stream, w.partial, nblocks, (int)r, one_int((int)r_old), w.sums, w.inv, scalars_out + 1, w.flag, scalars_out);

@@ -19,7 +19,6 @@
 // are both conflict-free) and written back once at the end, if a step accepted.  Otherwise the workgroup works on K_inv[b] in
 // global memory (L2-resident for one workgroup); after a rewrite: fence, barrier, fence before the next step reads it.
 // Z overlays the X rows / codes / nodes / r x r scratch, all dead by then; the X rows are staged again after a rewrite.
-#include <mutex>
 #include <type_traits>
 
 #include "common.h"
@@ -366,26 +365,6 @@ __global__ __launch_bounds__(SR_THREADS) void sweep_resident_kernel(SrArgs p) {
     }
 }
 
-int sr_set_lds_limit() {
-    static std::once_flag once[64];
-    static int status[64];
-    int dev = 0;
-    BARK_HIP_CHECK(hipGetDevice(&dev));
-    if (dev < 0 || dev >= 64) return fail(BARK_ERR_ARG, "device index %d out of range", dev);
-    std::call_once(once[dev], [dev]() {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(sweep_resident_kernel<true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)SR_LDS_MAX);
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(sweep_resident_kernel<false>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)SR_LDS_MAX);
-        status[dev] = (int)e;
-    });
-    if (status[dev] != 0)
-        return fail(BARK_ERR_HIP, "hipFuncSetAttribute(MaxDynamicSharedMemorySize) failed: %s",
-                    hipGetErrorString((hipError_t)status[dev]));
-    return BARK_OK;
-}
-
 #define SR_USE_OTHER "; use bark_tree_sweep_chains_hip (the multi-launch sweep) for this shape"
 
 // the limits on N, nc and d, and the plan; sets the error message
@@ -493,7 +472,10 @@ int bark_tree_sweep_resident_hip(bark_ctx *ctx, double *K_inv, int64_t N, int64_
     if (rc) return rc;
     if (!workspace || workspace_bytes < bark_tree_sweep_resident_workspace_bytes(N, 2, nc))
         return fail(BARK_ERR_WORKSPACE, "one-launch sweep: workspace too small");
-    if ((rc = sr_set_lds_limit())) return rc;
+    static const LdsLimit limits[] = {{reinterpret_cast<const void *>(sweep_resident_kernel<true>), SR_LDS_MAX},
+                                      {reinterpret_cast<const void *>(sweep_resident_kernel<false>), SR_LDS_MAX}};
+    static LdsLimitsOnce once;
+    if ((rc = raise_lds_limits(once, limits))) return rc;
     const SrArgs args{K_inv, (int)N, (int)nc, (int)n_steps, (int)d, static_cast<const unsigned char *>(packed),
                       static_cast<const int64_t *>(table_dev), X, s_dev, y, log_q_prior, log_u, state, accept_out, ctx->fault, plan};
     hipStream_t stream = static_cast<hipStream_t>(stream_);
