@@ -10,9 +10,11 @@
 //   acq_pack_kernel     upper triangle of M^-1, rows packed, followed by w: the image acq_scan_kernel stages in LDS
 //   acq_scan_kernel     one thread per candidate; the forests of the chunk in order, three running sums per candidate in
 //                       registers (sum of mu - kappa sd, of mu, of var + mu^2), kept in a (3, C) buffer between chunks
+//                       the target kinds (EI, PI, MES) instead keep one sum, of -(1/S) sum_s g(mu, sd, t_{b,s}), the
+//                       S targets of the forest read through wave-uniform addresses
 //   acq_finish_kernel   the acquisition value per candidate and per-workgroup (value, lowest index) minima;
 //   acq_best_kernel     reduces those (no float atomics: ties go to the lowest candidate index)
-// The order of every sum is fixed (leaves in code-bit order, forests 0 .. B-1), so the result depends neither on the chunk
+// The order of every sum is fixed (leaves in code-bit order, targets 0 .. S-1, forests 0 .. B-1), so the result depends neither on the chunk
 // nor on the variant: the LDS and the global variant of acq_scan_kernel run the same arithmetic on the same values.
 #include "common.h"
 
@@ -100,19 +102,66 @@ __global__ __launch_bounds__(ACQ_COND_THREADS) void acq_condition_kernel(const u
     }
 }
 
+// Utility of the target kinds (include/bark_hip.h) for one candidate and forest: -(1/S) sum_s g(mu, sd, t_s), s = 0 .. S-1.
+// What does not depend on the target is formed once: the reciprocal of the standard deviation and, for MES, log(sd E).
+// `t` is the same address in every lane (the forest's row of `targets`), so the loads are scalar.
+constexpr double ACQ_SQRT1_2 = 0.70710678118654752440;      // 1 / sqrt(2)
+constexpr double ACQ_INV_SQRT_2PI = 0.39894228040143267794;  // 1 / sqrt(2 pi)
+constexpr double ACQ_SQRT_2PI_E = 4.13273135412249293847;    // sqrt(2 pi e)
+
+template <int KIND>
+__device__ __forceinline__ double acq_target_term(double mu, double var, const double *__restrict__ t, int S) {
+    const double sd = sqrt(var > 0.0 ? var : 0.0);
+    double gs = 0.0;
+    if (KIND == BARK_ACQ_MES) {
+        const double inv = 1.0 / (sd + 1e-7);
+        const double h1 = log(sd * ACQ_SQRT_2PI_E);
+        for (int s = 0; s < S; ++s) {
+            const double gam = (t[s] - mu) * inv;
+            const double cdf = 0.5 * erfc(-gam * ACQ_SQRT1_2);
+            const double pdf = exp(-0.5 * (gam * gam)) * ACQ_INV_SQRT_2PI;
+            double inner = ACQ_SQRT_2PI_E * sd * cdf;
+            if (inner <= 0.0) inner = 1e-10;
+            gs += h1 - (log(inner) - gam * pdf / (2.0 * cdf + 1e-10));
+        }
+    } else if (sd > 0.0) {
+        const double inv = 1.0 / sd;
+        for (int s = 0; s < S; ++s) {
+            const double d = t[s] - mu;
+            const double z = d * inv;
+            const double cdf = 0.5 * erfc(-z * ACQ_SQRT1_2);
+            if (KIND == BARK_ACQ_EI)
+                gs += d * cdf + sd * (exp(-0.5 * (z * z)) * ACQ_INV_SQRT_2PI);
+            else
+                gs += cdf;
+        }
+    } else {  // a point mass at mu; a NaN target stays NaN
+        for (int s = 0; s < S; ++s) {
+            const double d = t[s] - mu;
+            if (KIND == BARK_ACQ_EI)
+                gs += d < 0.0 ? 0.0 : d;
+            else
+                gs += d > 0.0 ? 1.0 : (d <= 0.0 ? 0.0 : d);
+        }
+    }
+    return -(gs / (double)S);
+}
+
 // LDS_TABLE: the forest's image sits in LDS ([tri + R] doubles) in front of the tile's leaf lists ([m][ACQ_TILE] 16-bit
 // ids, lane fastest: conflict-free); otherwise only the lists do and M^-1 / w are read from global memory.  A wave's 64
 // candidates walk the tree pairs (j, i) in lock step, so their table reads fall into the leaves(tree j) x leaves(tree i)
 // block of M^-1: for prior-sized trees a handful of distinct addresses, which the LDS broadcasts.
 // n: candidates of this slab (ccodes (bc, W, cpad) holds their codes), acc: the slab's part of the (3, C) sums, row stride
 // `astride`; first: this is the first chunk of forests (the sums start at zero).
-template <bool LDS_TABLE>
+// KIND: BARK_ACQ_LCB_MEAN for both confidence bounds (three sums; kappa), or a target kind (row 0 of acc only; targets (bc, S)).
+template <bool LDS_TABLE, int KIND>
 __global__ __launch_bounds__(ACQ_TILE) void acq_scan_kernel(const uint32_t *__restrict__ ccodes, int W, int cpad, int n,
                                                             const double *__restrict__ wvec, const double *__restrict__ Minv,
                                                             const double *__restrict__ tab, int R,
                                                             const double *__restrict__ noise, const double *__restrict__ scale,
-                                                            int m, int bc, double kappa, int first, double *__restrict__ acc,
-                                                            size_t astride) {
+                                                            int m, int bc, double kappa, const double *__restrict__ targets,
+                                                            int S, int first, double *__restrict__ acc, size_t astride) {
+    constexpr bool LCB = KIND == BARK_ACQ_LCB_MEAN;
     extern __shared__ double smem[];
     const int tid = threadIdx.x;
     const int c = blockIdx.x * ACQ_TILE + tid;
@@ -122,8 +171,10 @@ __global__ __launch_bounds__(ACQ_TILE) void acq_scan_kernel(const uint32_t *__re
     double a0 = 0.0, a1 = 0.0, a2 = 0.0;
     if (active && !first) {
         a0 = acc[c];
-        a1 = acc[astride + c];
-        a2 = acc[2 * astride + c];
+        if (LCB) {
+            a1 = acc[astride + c];
+            a2 = acc[2 * astride + c];
+        }
     }
     for (int b = 0; b < bc; ++b) {
         if (LDS_TABLE) {
@@ -170,14 +221,20 @@ __global__ __launch_bounds__(ACQ_TILE) void acq_scan_kernel(const uint32_t *__re
         const double sc = scale[b];
         const double mu = sc / ((double)m * sigma2) * s1;
         const double var = sc / (double)m * (dg + 2.0 * off);
-        a0 += mu - kappa * sqrt(var > 0.0 ? var : 0.0);
-        a1 += mu;
-        a2 += var + mu * mu;
+        if (LCB) {
+            a0 += mu - kappa * sqrt(var > 0.0 ? var : 0.0);
+            a1 += mu;
+            a2 += var + mu * mu;
+        } else {
+            a0 += acq_target_term<KIND>(mu, var, targets + (size_t)b * S, S);
+        }
     }
     if (active) {
         acc[c] = a0;
-        acc[astride + c] = a1;
-        acc[2 * astride + c] = a2;
+        if (LCB) {
+            acc[astride + c] = a1;
+            acc[2 * astride + c] = a2;
+        }
     }
 }
 
@@ -210,7 +267,8 @@ __device__ __forceinline__ void block_min(double &v, long long &i, double *rv, l
 constexpr long long ACQ_NO_INDEX = 0x7fffffffffffffffLL;
 
 // kind 0: mean over the forests of mu - kappa sd (the reference's calculate_acqf, tests/optimization/test_optimality.py);
-// kind 1: the lower confidence bound of the moment-matched mixture (tree_gps.py:116-131)
+// kind 1: the lower confidence bound of the moment-matched mixture (tree_gps.py:116-131);
+// the target kinds: mean over the forests of the scan's one sum, like kind 0
 // skip (n_skip entries): candidates that keep their value in acq_out but never win the minimum
 __global__ __launch_bounds__(256) void acq_finish_kernel(const double *__restrict__ acc, long long C, int B, double kappa,
                                                          int kind, const long long *__restrict__ skip, int n_skip,
@@ -222,7 +280,7 @@ __global__ __launch_bounds__(256) void acq_finish_kernel(const double *__restric
     double v = INFINITY;
     long long i = ACQ_NO_INDEX;
     if (c < C) {
-        if (kind == BARK_ACQ_LCB_MEAN) {
+        if (kind != BARK_ACQ_LCB_MIXTURE) {
             v = acc[c] / (double)B;
         } else {
             const double mu = acc[C + c] / (double)B;
@@ -275,11 +333,25 @@ size_t scan_lds_bytes(int64_t R, int64_t m, bool lds_table) {
 
 size_t acq_condition_lds_bytes(int64_t R) { return ((size_t)R + 1) * sizeof(double) + (ACQ_MAX_TREES + 2) * sizeof(int); }
 
-// The two kernels of this unit that can use more than 64 KiB of dynamic LDS: the LDS variant of the scan (up to a whole CU's)
+// the instantiation of a variant and kind; both confidence bounds share one (they differ in the finish only)
+using ScanKernel = decltype(&acq_scan_kernel<true, BARK_ACQ_LCB_MEAN>);
+ScanKernel scan_kernel(bool lds, int kind) {
+    switch (kind) {
+        case BARK_ACQ_EI: return lds ? acq_scan_kernel<true, BARK_ACQ_EI> : acq_scan_kernel<false, BARK_ACQ_EI>;
+        case BARK_ACQ_PI: return lds ? acq_scan_kernel<true, BARK_ACQ_PI> : acq_scan_kernel<false, BARK_ACQ_PI>;
+        case BARK_ACQ_MES: return lds ? acq_scan_kernel<true, BARK_ACQ_MES> : acq_scan_kernel<false, BARK_ACQ_MES>;
+        default: return lds ? acq_scan_kernel<true, BARK_ACQ_LCB_MEAN> : acq_scan_kernel<false, BARK_ACQ_LCB_MEAN>;
+    }
+}
+
+// The kernels of this unit that can use more than 64 KiB of dynamic LDS: the LDS variant of the scan, every kind (up to a whole CU's),
 // and acq_condition_kernel at the largest R the leaf-space path admits (8192: 264 bytes past 64 KiB).  acq_condition and
 // acq_scan call this before they launch.
 int raise_acq_lds_limits() {
-    static const LdsLimit limits[] = {{reinterpret_cast<const void *>(acq_scan_kernel<true>), ACQ_LDS_MAX},
+    static const LdsLimit limits[] = {{reinterpret_cast<const void *>(scan_kernel(true, BARK_ACQ_LCB_MEAN)), ACQ_LDS_MAX},
+                                      {reinterpret_cast<const void *>(scan_kernel(true, BARK_ACQ_EI)), ACQ_LDS_MAX},
+                                      {reinterpret_cast<const void *>(scan_kernel(true, BARK_ACQ_PI)), ACQ_LDS_MAX},
+                                      {reinterpret_cast<const void *>(scan_kernel(true, BARK_ACQ_MES)), ACQ_LDS_MAX},
                                       {reinterpret_cast<const void *>(acq_condition_kernel), acq_condition_lds_bytes(8192)}};
     static LdsLimitsOnce once;
     return raise_lds_limits(once, limits);
@@ -308,19 +380,18 @@ int acq_pack(const double *Minv, const double *w, int R, int bc, double *tab, hi
     return BARK_OK;
 }
 
-// variant: 1 LDS, 2 global (resolved by bark_acquisition_plan); n candidates of one slab against the bc forests of the chunk
-int acq_scan(int variant, const uint32_t *ccodes, int W, int cpad, int n, const double *wvec, const double *Minv,
-             const double *tab, int R, const double *noise, const double *scale, int m, int bc, double kappa, int first,
-             double *acc, size_t astride, hipStream_t s) {
+// variant: 1 LDS, 2 global (resolved by bark_acquisition_plan); n candidates of one slab against the bc forests of the chunk.
+// kind: BARK_ACQ_*; both confidence bounds run the same kernel, the target kinds read targets (bc, S).
+int acq_scan(int variant, int kind, const uint32_t *ccodes, int W, int cpad, int n, const double *wvec, const double *Minv,
+             const double *tab, int R, const double *noise, const double *scale, int m, int bc, double kappa, const double *targets,
+             int S, int first, double *acc, size_t astride, hipStream_t s) {
     const dim3 g((unsigned)((n + ACQ_TILE - 1) / ACQ_TILE));
     const int rc = raise_acq_lds_limits();
     if (rc) return rc;
-    if (variant == 1)
-        hipLaunchKernelGGL(acq_scan_kernel<true>, g, dim3(ACQ_TILE), scan_lds_bytes(R, m, true), s, ccodes, W, cpad, n, wvec, Minv,
-                           tab, R, noise, scale, m, bc, kappa, first, acc, astride);
-    else
-        hipLaunchKernelGGL(acq_scan_kernel<false>, g, dim3(ACQ_TILE), scan_lds_bytes(R, m, false), s, ccodes, W, cpad, n, wvec,
-                           Minv, tab, R, noise, scale, m, bc, kappa, first, acc, astride);
+    const bool lds = variant == 1;
+    const size_t bytes = scan_lds_bytes(R, m, lds);
+    hipLaunchKernelGGL(scan_kernel(lds, kind), g, dim3(ACQ_TILE), bytes, s, ccodes, W, cpad, n, wvec, Minv, tab, R, noise, scale, m, bc,
+                       kappa, targets, S, first, acc, astride);
     BARK_LAUNCH_CHECK();
     return BARK_OK;
 }

@@ -1385,7 +1385,7 @@ LeafNeeds samples_needs(int64_t C, int64_t S) {  // draws need V and w, not M^-1
     q.S = S;
     return q;
 }
-constexpr int64_t ACQ_MAX_PENDING = 64, ACQ_MAX_SKIP = 64;
+constexpr int64_t ACQ_MAX_PENDING = 64, ACQ_MAX_SKIP = 64, ACQ_MAX_TARGETS = 1024;
 
 LeafNeeds scan_needs(int64_t C, int64_t P) {  // the posterior's areas with the codes of one slab of candidates
     LeafNeeds q = mll_needs(C < ACQ_SLAB ? C : ACQ_SLAB);
@@ -1544,6 +1544,11 @@ size_t bark_acquisition_scan_pending_workspace_bytes(int64_t N, int64_t max_bits
     return leaf_areas(nullptr, N, max_bits, m, Bc, scan_needs(C, P)).total;
 }
 
+// the targets stay where the caller has them: nothing is added to the workspace
+size_t bark_acquisition_scan_targets_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t Bc, int64_t C, int64_t P) {
+    return bark_acquisition_scan_pending_workspace_bytes(N, max_bits, m, Bc, C, P);
+}
+
 int bark_mll_leafspace_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d,
                            const double *y, const double *noise, const double *scale, int flags, const double *cand,
                            int64_t C, double *mll_out, double *mu_out, double *var_out, int32_t *info_out,
@@ -1641,12 +1646,14 @@ int bark_posterior_samples_hip(bark_ctx *ctx, const void *packed, const bark_pac
 
 // Acquisition scan (include/bark_hip.h, kernels in acquire.hip): w and M^-1 of a chunk of forests are consumed by
 // acq_scan_kernel slab by slab of candidates before the next chunk is prepared; the finish after the last chunk.  With pending
-// points M^-1 is conditioned on them first (acq_condition_kernel), so neither variant of the scan knows about them.
-int bark_acquisition_scan_pending_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N,
+// points M^-1 is conditioned on them first (acq_condition_kernel), so neither variant of the scan knows about them, and no
+// kind does.  The target kinds read the chunk's rows of `targets` (B, S) in the scan.
+int bark_acquisition_scan_targets_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N,
                                       int64_t d, const double *y, const double *noise, const double *scale, const double *cand,
                                       int64_t C, const double *pending, int64_t P, const int64_t *skip_idx, int64_t n_skip,
-                                      double kappa, int kind, int variant, double *acq_out, double *best_out, int64_t *idx_out,
-                                      int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc, void *stream_) {
+                                      const double *targets, int64_t S, double kappa, int kind, int variant, double *acq_out,
+                                      double *best_out, int64_t *idx_out, int32_t *info_out, void *workspace,
+                                      size_t workspace_bytes, int64_t Bc, void *stream_) {
     error_buffer()[0] = 0;
     if (!info || !scale || !cand || !best_out || !idx_out) return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: null argument");
     if (C < 1) return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: bad shape C=%lld", (long long)C);
@@ -1654,8 +1661,12 @@ int bark_acquisition_scan_pending_hip(bark_ctx *ctx, const void *packed, const b
         return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: at most %lld pending points and %lld skipped candidates (got %lld, %lld)",
                     (long long)ACQ_MAX_PENDING, (long long)ACQ_MAX_SKIP, (long long)P, (long long)n_skip);
     if ((P > 0 && !pending) || (n_skip > 0 && !skip_idx)) return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: null argument");
-    if (kind != BARK_ACQ_LCB_MEAN && kind != BARK_ACQ_LCB_MIXTURE)
-        return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: unknown kind %d", kind);
+    if (kind < BARK_ACQ_LCB_MEAN || kind > BARK_ACQ_MES) return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: unknown kind %d", kind);
+    const bool lcb = kind == BARK_ACQ_LCB_MEAN || kind == BARK_ACQ_LCB_MIXTURE;
+    if (!lcb && !targets) return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: kind %d needs targets", kind);
+    if (!lcb && (S < 1 || S > ACQ_MAX_TARGETS))
+        return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: between 1 and %lld targets per forest (got %lld)",
+                    (long long)ACQ_MAX_TARGETS, (long long)S);
     if (!std::isfinite(kappa)) return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: kappa is not finite");
     int var = 0, rc;
     if ((rc = bark_acquisition_plan(info->max_bits, info->m, variant, &var, nullptr))) return rc;
@@ -1677,8 +1688,9 @@ int bark_acquisition_scan_pending_hip(bark_ctx *ctx, const void *packed, const b
         for (int64_t s0 = 0; s0 < C; s0 += ACQ_SLAB) {
             const int64_t n = C - s0 < ACQ_SLAB ? C - s0 : ACQ_SLAB;
             if ((r = sys.walk_candidates(cand + (size_t)s0 * d, n))) return r;
-            r = acq_scan(var, a.ccodes, sys.W, (int)bark_leaf_npad(n), (int)n, a.w, a.Minv, a.tab, sys.R, noise + c0, scale + c0, sys.m,
-                         sys.bc, kappa, c0 == 0, a.acc + s0, (size_t)C, sys.caller);
+            r = acq_scan(var, lcb ? BARK_ACQ_LCB_MEAN : kind, a.ccodes, sys.W, (int)bark_leaf_npad(n), (int)n, a.w, a.Minv, a.tab, sys.R,
+                         noise + c0, scale + c0, sys.m, sys.bc, kappa, lcb ? nullptr : targets + (size_t)c0 * S, lcb ? 0 : (int)S,
+                         c0 == 0, a.acc + s0, (size_t)C, sys.caller);
             if (r) return r;
         }
         return sys.close_chunk();
@@ -1686,6 +1698,20 @@ int bark_acquisition_scan_pending_hip(bark_ctx *ctx, const void *packed, const b
     if (rc) return rc;
     return acq_finish(a.acc, C, (int)sys.B, kappa, kind, skip_idx, (int)n_skip, acq_out, a.part, a.part_i, info_out, best_out, idx_out,
                       sys.caller);
+}
+
+// the confidence bounds only: the two entry points without targets refuse every other kind
+int bark_acquisition_scan_pending_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N,
+                                      int64_t d, const double *y, const double *noise, const double *scale, const double *cand,
+                                      int64_t C, const double *pending, int64_t P, const int64_t *skip_idx, int64_t n_skip,
+                                      double kappa, int kind, int variant, double *acq_out, double *best_out, int64_t *idx_out,
+                                      int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc, void *stream_) {
+    error_buffer()[0] = 0;
+    if (kind != BARK_ACQ_LCB_MEAN && kind != BARK_ACQ_LCB_MIXTURE)
+        return fail(BARK_ERR_ARG, "bark_acquisition_scan_hip: unknown kind %d", kind);
+    return bark_acquisition_scan_targets_hip(ctx, packed, info, X, N, d, y, noise, scale, cand, C, pending, P, skip_idx, n_skip, nullptr,
+                                             0, kappa, kind, variant, acq_out, best_out, idx_out, info_out, workspace, workspace_bytes,
+                                             Bc, stream_);
 }
 
 int bark_acquisition_scan_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d,

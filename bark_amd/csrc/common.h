@@ -137,10 +137,11 @@ int acq_condition(const uint32_t *pcodes, int W, int ppad, int P, double *Minv, 
                   int m, int bc, const int32_t *info, hipStream_t s);
 // image of the chunk for the LDS variant
 int acq_pack(const double *Minv, const double *w, int R, int bc, double *tab, hipStream_t s);
-// variant: 1 LDS, 2 global (resolved by bark_acquisition_plan); n candidates of one slab against the bc forests of the chunk
-int acq_scan(int variant, const uint32_t *ccodes, int W, int cpad, int n, const double *wvec, const double *Minv,
-             const double *tab, int R, const double *noise, const double *scale, int m, int bc, double kappa, int first,
-             double *acc, size_t astride, hipStream_t s);
+// variant: 1 LDS, 2 global (resolved by bark_acquisition_plan); n candidates of one slab against the bc forests of the chunk;
+// kind: BARK_ACQ_*, the target kinds with the chunk's targets (bc, S)
+int acq_scan(int variant, int kind, const uint32_t *ccodes, int W, int cpad, int n, const double *wvec, const double *Minv,
+             const double *tab, int R, const double *noise, const double *scale, int m, int bc, double kappa, const double *targets,
+             int S, int first, double *acc, size_t astride, hipStream_t s);
 int acq_finish(const double *acc, int64_t C, int B, double kappa, int kind, const int64_t *skip, int n_skip, double *acq_out,
                double *part_v, int64_t *part_i, const int32_t *info, double *best, int64_t *best_i, hipStream_t s);
 

@@ -3,4 +3,4 @@ posterior draws of `bark_amd.tree_kernels.posterior_samples`, and the acquisitio
 in for the reference's solver-based `propose` (`acquisition`)."""
 
 from .acquisition import (acquisition_plan, acquisition_scan, propose_batch_from_candidates,  # noqa: F401
-                          propose_from_candidates)
+                          propose_from_candidates, propose_mes_from_candidates)

@@ -23,10 +23,13 @@ from .. import _lib
 from ..fitting.mll import _feat_types_of, _forest3, _leaf_call, _leaf_inputs
 from ..forest import _is_torch, _points
 
-KINDS = {"lcb_mean": _lib.ACQ_LCB_MEAN, "lcb_mixture": _lib.ACQ_LCB_MIXTURE}
+KINDS = {"lcb_mean": _lib.ACQ_LCB_MEAN, "lcb_mixture": _lib.ACQ_LCB_MIXTURE, "ei": _lib.ACQ_EI, "pi": _lib.ACQ_PI,
+         "mes": _lib.ACQ_MES}
+TARGET_KINDS = ("ei", "pi", "mes")  # the utilities of (mu_b, sd_b, target): bark_acquisition_scan_targets_hip
 VARIANTS = {"auto": 0, "lds": 1, "global": 2}
 MAX_TREES, MAX_LEAVES = 64, 8192  # limits of the leaf-space posterior (include/bark_hip.h)
 MAX_PENDING = MAX_SKIP = 64  # limits of bark_acquisition_scan_pending_hip
+MAX_TARGETS = 1024  # ... of bark_acquisition_scan_targets_hip, per forest
 
 
 def acquisition_plan(max_bits: int, m: int, variant: str = "auto") -> dict:
@@ -59,8 +62,31 @@ def _skip_indices(skip, C: int):
     return t.contiguous() if t.numel() else None
 
 
+def _target_matrix(targets, B: int, kind: str, train_y):
+    """-> (B, S) float64 targets, numpy or torch as given: a scalar is every forest's one target, (B,) one target per
+    forest; None is the incumbent min(train_y) for "ei" / "pi".  Shapes are checked here, before anything needs a device."""
+    if targets is None:
+        if kind == "mes":
+            raise ValueError("kind='mes' needs targets: draws of the minimum, e.g. from generate_fstar_samples")
+        targets = train_y.min() if _is_torch(train_y) else np.min(np.asarray(train_y, dtype=np.float64))
+    if _is_torch(targets):
+        import torch
+
+        t = targets.to(torch.float64)
+        t = t.reshape(1, 1).expand(B, 1) if t.ndim == 0 else t.reshape(-1, 1) if t.ndim == 1 else t
+    else:
+        t = np.array(targets, dtype=np.float64)  # a copy: the caller's array may be read-only
+        t = np.broadcast_to(t.reshape(1, 1), (B, 1)) if t.ndim == 0 else t.reshape(-1, 1) if t.ndim == 1 else t
+    if t.ndim != 2 or t.shape[0] != B:
+        raise ValueError(f"targets must be a scalar, ({B},) or ({B}, S): one row per forest (got shape {tuple(t.shape)})")
+    if not 1 <= t.shape[1] <= MAX_TARGETS:
+        raise ValueError(f"between 1 and {MAX_TARGETS} targets per forest (got {t.shape[1]})")
+    return t
+
+
 def acquisition_scan(model, data, candidates, domain, kappa: float = 1.96, kind: str = "lcb_mean",
-                     return_values: bool = False, chunk: int | None = None, variant: str = "auto", pending=None, skip=None):
+                     return_values: bool = False, chunk: int | None = None, variant: str = "auto", pending=None, skip=None,
+                     targets=None):
     """-> (best_value, best_index[, acq (C,)]): the minimum over the candidates of the acquisition and its index (ties:
     the lowest index); with `return_values` also the acquisition of every candidate.
 
@@ -68,6 +94,14 @@ def acquisition_scan(model, data, candidates, domain, kappa: float = 1.96, kind:
     feat_types — as `forest_predict` takes them.  kind="lcb_mean": the reference's acqf above; kind="lcb_mixture":
     mu_mix - kappa sqrt(var_mix) with the moments of `mixture_of_gaussians_as_normal`.  variant: "auto", or "lds" /
     "global" to force the scan kernel that keeps a forest's M^-1 in LDS / reads it from global memory (`acquisition_plan`).
+
+    kind="ei" | "pi" | "mes": expected improvement, probability of improvement and min-value entropy search (the
+    reference's `information_gain` at the target fidelity, information_based_fidelity.py:39-87) below `targets`, each the
+    mean over forests b and targets s of g(mu_b(x), sd_b(x), t[b][s]); include/bark_hip.h has the formulas.  The call
+    returns the negated utility, so the minimum is the utility's maximiser; `kappa` is not used.  targets: a scalar, (B,)
+    or (B, S <= 1024), numpy or torch (a device tensor is read where it is); None is the incumbent min(train_y) for "ei" and
+    "pi", and refused for "mes", whose targets are draws of the minimum (`generate_fstar_samples`,
+    `propose_mes_from_candidates`).  A NaN target gives NaN values and (NaN, -1).  The other kinds ignore `targets`.
 
     The sums run in a fixed order (a candidate's leaves in tree order, forests 0 .. B-1), so the result does not depend
     on `chunk` or `variant`, bit for bit.  At most 64 trees and 8192 leaves per forest.  Extra device memory is the
@@ -88,7 +122,7 @@ def acquisition_scan(model, data, candidates, domain, kappa: float = 1.96, kind:
     vector.  ValueError for an invalid categorical value, LinAlgError for a forest whose leaf-space system is not positive
     definite; there is no CPU fallback (RuntimeError without a GPU)."""
     if kind not in KINDS:
-        raise ValueError(f"unknown kind {kind!r} (use 'lcb_mean' or 'lcb_mixture')")
+        raise ValueError(f"unknown kind {kind!r} (use 'lcb_mean', 'lcb_mixture', 'ei', 'pi' or 'mes')")
     if variant not in VARIANTS:
         raise ValueError(f"unknown variant {variant!r} (use 'auto', 'lds' or 'global')")
     kappa = float(kappa)
@@ -102,6 +136,7 @@ def acquisition_scan(model, data, candidates, domain, kappa: float = 1.96, kind:
         raise ValueError(f"acquisition scan supports at most {MAX_TREES} trees (got {m})")
     if len(candidates) < 1:
         raise ValueError("acquisition scan needs at least one candidate")
+    tgt = _target_matrix(targets, int(nodes3.shape[0]), kind, train_y) if kind in TARGET_KINDS else None
 
     import torch
 
@@ -114,7 +149,7 @@ def acquisition_scan(model, data, candidates, domain, kappa: float = 1.96, kind:
     best = torch.empty((), dtype=torch.float64, device=dev)
     idx = torch.empty((), dtype=torch.int64, device=dev)
     lib = _lib.lib()
-    if pending is None and skip is None:
+    if pending is None and skip is None and tgt is None:
         _leaf_call(q, lib.bark_acquisition_scan_hip, lambda k: int(lib.bark_acquisition_scan_workspace_bytes(q.N, R, q.pf.m, k, C)),
                    chunk, _lib.ptr(q.cand_d), C, kappa, KINDS[kind], VARIANTS[variant], _lib.ptr(acq), _lib.ptr(best), _lib.ptr(idx))
     else:
@@ -123,10 +158,17 @@ def acquisition_scan(model, data, candidates, domain, kappa: float = 1.96, kind:
         if P > MAX_PENDING:
             raise ValueError(f"acquisition scan supports at most {MAX_PENDING} pending points (got {P})")
         skip_d = None if skip is None else _skip_indices(skip, C)
-        _leaf_call(q, lib.bark_acquisition_scan_pending_hip,
-                   lambda k: int(lib.bark_acquisition_scan_pending_workspace_bytes(q.N, R, q.pf.m, k, C, P)), chunk,
-                   _lib.ptr(q.cand_d), C, _lib.ptr(pend_d), P, _lib.ptr(skip_d), 0 if skip_d is None else int(skip_d.numel()),
-                   kappa, KINDS[kind], VARIANTS[variant], _lib.ptr(acq), _lib.ptr(best), _lib.ptr(idx))
+        shared = (_lib.ptr(q.cand_d), C, _lib.ptr(pend_d), P, _lib.ptr(skip_d), 0 if skip_d is None else int(skip_d.numel()))
+        outs = (kappa, KINDS[kind], VARIANTS[variant], _lib.ptr(acq), _lib.ptr(best), _lib.ptr(idx))
+        if tgt is None:
+            _leaf_call(q, lib.bark_acquisition_scan_pending_hip,
+                       lambda k: int(lib.bark_acquisition_scan_pending_workspace_bytes(q.N, R, q.pf.m, k, C, P)), chunk,
+                       *shared, *outs)
+        else:
+            tgt_d = _lib.to_device(tgt, torch.float64)
+            _leaf_call(q, lib.bark_acquisition_scan_targets_hip,
+                       lambda k: int(lib.bark_acquisition_scan_targets_workspace_bytes(q.N, R, q.pf.m, k, C, P)), chunk,
+                       *shared, _lib.ptr(tgt_d), int(tgt_d.shape[1]), *outs)
     if _is_torch(candidates):
         return (best, idx, acq) if return_values else (best, idx)
     out = (float(best.item()), int(idx.item()))
@@ -134,21 +176,24 @@ def acquisition_scan(model, data, candidates, domain, kappa: float = 1.96, kind:
 
 
 def propose_from_candidates(model, data, candidates, domain, kappa: float = 1.96, kind: str = "lcb_mean",
-                            chunk: int | None = None, variant: str = "auto"):
+                            chunk: int | None = None, variant: str = "auto", targets=None):
     """The candidate row that minimises the acquisition (`acquisition_scan`): what the reference's `propose` returns when
     its search space is the given candidate set, and a better stand-in than its single random candidate when no solver is
-    available.  Torch candidates give a device row (the index is not read back), numpy candidates a numpy row."""
-    _, idx = acquisition_scan(model, data, candidates, domain, kappa=kappa, kind=kind, chunk=chunk, variant=variant)
+    available.  `targets`: those of kind "ei" / "pi" / "mes".  Torch candidates give a device row (the index is not read
+    back), numpy candidates a numpy row."""
+    _, idx = acquisition_scan(model, data, candidates, domain, kappa=kappa, kind=kind, chunk=chunk, variant=variant,
+                              targets=targets)
     if _is_torch(candidates):
         return candidates.index_select(0, idx.to(candidates.device).reshape(1))[0]
     return np.asarray(candidates)[idx]
 
 
 def propose_batch_from_candidates(model, data, candidates, domain, q: int, kappa: float = 1.96, kind: str = "lcb_mean",
-                                  pending=None, chunk: int | None = None, variant: str = "auto"):
+                                  pending=None, chunk: int | None = None, variant: str = "auto", targets=None):
     """-> (rows (q, d), indices (q,)): q distinct candidate rows chosen greedily.  Pick k is the arg-min of the scan
     conditioned on `pending` followed by picks 0 .. k-1 (`acquisition_scan(pending=..., skip=...)`), with those picks
     excluded: a point that is being evaluated no longer attracts the next one, because its variance has collapsed.
+    With kind="ei" that is a greedy expected-improvement batch under the kriging believer; `targets` are the same for every pick.
 
     A plain loop of q scans with no state kept between the picks, so the cost is q times one scan.  Torch candidates
     give device tensors (a pick is gathered with index_select; no index is read back), numpy candidates numpy arrays.
@@ -177,7 +222,7 @@ def propose_batch_from_candidates(model, data, candidates, domain, q: int, kappa
             cur = pend if not rows else np.concatenate(([] if pend is None else [pend]) + [np.stack(rows)])
             skip = picks or None
         _, idx = acquisition_scan(model, data, candidates, domain, kappa=kappa, kind=kind, chunk=chunk, variant=variant,
-                                  pending=cur, skip=skip)
+                                  pending=cur, skip=skip, targets=targets)
         if on_device:
             idx = idx.to(candidates.device)
             rows.append(candidates.index_select(0, idx.reshape(1))[0])
@@ -187,3 +232,27 @@ def propose_batch_from_candidates(model, data, candidates, domain, q: int, kappa
     if on_device:
         return torch.stack(rows), torch.stack(picks)
     return np.stack(rows), np.asarray(picks, dtype=np.int64)
+
+
+def propose_mes_from_candidates(model, data, candidates, domain, num_samples: int = 100, generator=None,
+                                chunk: int | None = None, variant: str = "auto", pending=None, skip=None):
+    """The candidate row with the largest information gain about the minimum value: the workflow of the reference's
+    `propose_fidelity_information_based` (information_based_fidelity.py:16-36) with a candidate set in place of its single x.
+    `generate_fstar_samples` draws num_samples joint posterior samples per forest at the training inputs and keeps their
+    minima, (B, num_samples) on the device; `acquisition_scan(kind="mes", targets=...)` scores every candidate against
+    them and returns the arg-min of the negated gain.  generator: a torch.Generator, an int seed or None, as
+    `generate_fstar_samples` takes it.  Torch candidates give a device row (the index is not read back), numpy
+    candidates a numpy row."""
+    import torch
+
+    from .thompson_sampling import generate_fstar_samples
+
+    train_x, train_y = data
+    # torch inputs keep the minima on the device between the two calls
+    site_x = train_x if _is_torch(train_x) else torch.as_tensor(np.asarray(train_x, dtype=np.float64), device=_lib.torch_device())
+    fstar = generate_fstar_samples(model, (site_x, train_y), domain, num_samples=num_samples, generator=generator)
+    _, idx = acquisition_scan(model, data, candidates, domain, kind="mes", targets=fstar, chunk=chunk, variant=variant,
+                              pending=pending, skip=skip)
+    if _is_torch(candidates):
+        return candidates.index_select(0, idx.to(candidates.device).reshape(1))[0]
+    return np.asarray(candidates)[idx]

@@ -371,6 +371,9 @@ int bark_posterior_samples_hip(bark_ctx *ctx, const void *packed, const bark_pac
  * ------------------------------------------------------------------------------------- */
 #define BARK_ACQ_LCB_MEAN 0
 #define BARK_ACQ_LCB_MIXTURE 1
+#define BARK_ACQ_EI 2  /* the target kinds: bark_acquisition_scan_targets_hip only */
+#define BARK_ACQ_PI 3
+#define BARK_ACQ_MES 4
 size_t bark_acquisition_scan_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t Bc, int64_t C);
 int bark_acquisition_plan(int64_t max_bits, int64_t m, int variant /* 0 auto, 1 LDS, 2 global */, int *variant_out,
                           int64_t *lds_bytes_out);
@@ -383,6 +386,7 @@ int bark_acquisition_scan_hip(bark_ctx *ctx, const void *packed, const bark_pack
 /* ---------------------------------------------------------------------------------------
  * Acquisition scan conditioned on pending points, with candidates excluded from the arg-min: what a batch of proposals
  * needs ("these points are being evaluated already").  bark_acquisition_scan_hip is the P = 0, n_skip = 0 call of it.
+ * Both take the confidence bounds only (kind 0 / 1); the kinds that need targets go through bark_acquisition_scan_targets_hip.
  * pending: (P, d) device, or NULL with P = 0.  Each pending point x* is treated as observed at the forest's own posterior
  * mean ("kriging believer"), with the same noise.  With M = I_R + c Z'Z, w = M^-1 Z'y, c = scale / (m s2) as above and z the
  * one-hot row of x* (its m leaves L(x*) set), per forest:
@@ -408,6 +412,43 @@ int bark_acquisition_scan_pending_hip(bark_ctx *ctx, const void *packed, const b
                                       int64_t C, const double *pending /* (P, d) or NULL */, int64_t P,
                                       const int64_t *skip_idx /* (n_skip,) or NULL */, int64_t n_skip, double kappa, int kind,
                                       int variant, double *acq_out /* (C,) or NULL */, double *best_out /* 1 */,
+                                      int64_t *idx_out /* 1 */, int32_t *info_out /* (B,) */, void *workspace,
+                                      size_t workspace_bytes, int64_t Bc, void *stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Acquisition scan against targets: expected improvement, probability of improvement and min-value entropy search (the
+ * reference's information gain at the target fidelity, information_based_fidelity.py:39-87, fed by the minima of joint
+ * draws, thompson_sampling.generate_fstar_samples), next to the confidence bounds.  bark_acquisition_scan_pending_hip is the
+ * targets = NULL call of it; kinds 0 / 1 ignore targets and S.
+ * targets: (B, S) device, row b the targets t_{b,s} of forest b (an incumbent, or draws of the minimum f*).  The library
+ * minimises, so every target kind returns the negated utility and best_out / idx_out name the maximiser of the utility
+ * (ties: the lowest index; NaN never wins).  With mu = mu_b(x), var = var_b(x) exactly as the scan forms them above,
+ * sd = sqrt(max(var, 0)), t = t_{b,s}, Phi(z) = 0.5 erfc(-z / sqrt 2), phi(z) = exp(-z^2 / 2) / sqrt(2 pi), E = sqrt(2 pi e):
+ *   BARK_ACQ_EI:   z = (t - mu) / sd,  g = (t - mu) Phi(z) + sd phi(z);        sd == 0: g = max(t - mu, 0)
+ *   BARK_ACQ_PI:   g = Phi(z);                                                 sd == 0: g = t > mu ? 1 : 0
+ *   BARK_ACQ_MES:  gam = (t - mu) / (sd + 1e-7), cdf = Phi(gam), pdf = phi(gam), inner = E sd cdf (1e-10 where inner <= 0),
+ *                  g = log(sd E) - ( log(inner) - gam pdf / (2 cdf + 1e-10) )   -- the reference's formula with its guards;
+ *                  sd == 0 gives g = -inf, an acquisition of +inf: such a candidate never wins
+ *   acq[x] = -(1/B) sum_b ( (1/S) sum_s g )
+ * in fp64 with the device library's erfc, exp and log.  The quotients by sd and sd + 1e-7 are products with one reciprocal
+ * per (candidate, forest); 1 / sqrt 2 and 1 / sqrt(2 pi) are constants.  A NaN target makes the acquisition of every
+ * candidate NaN (under sd == 0 too), so none wins.
+ * Summation order (part of the contract): s = 0 .. S-1 within a forest, then the division by S; forests strictly
+ * b = 0 .. B-1 across chunks, the division by B in the finish.  As for the confidence bounds the result depends neither on
+ * Bc nor on the variant, bit for bit.  S targets repeated k times agree with the S targets to rounding only.
+ * kappa is ignored by the target kinds but must still be finite.  Pending points and skip_idx act as described above: the
+ * conditioning comes before the scan and does not know the kind.
+ * Limits, refused with BARK_ERR_ARG before any launch: the pending entry point's; unknown kind; a target kind with
+ * targets == NULL, S < 1 or S > 1024.  The call only enqueues.  No memory beyond the pending entry point's: the targets are
+ * read where they are, through wave-uniform addresses, and the plan (bark_acquisition_plan) is that of the other kinds.
+ * ------------------------------------------------------------------------------------- */
+size_t bark_acquisition_scan_targets_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t Bc, int64_t C, int64_t P);
+int bark_acquisition_scan_targets_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N,
+                                      int64_t d, const double *y, const double *noise, const double *scale, const double *cand,
+                                      int64_t C, const double *pending /* (P, d) or NULL */, int64_t P,
+                                      const int64_t *skip_idx /* (n_skip,) or NULL */, int64_t n_skip,
+                                      const double *targets /* (B, S) or NULL for kinds 0 / 1 */, int64_t S, double kappa,
+                                      int kind, int variant, double *acq_out /* (C,) or NULL */, double *best_out /* 1 */,
                                       int64_t *idx_out /* 1 */, int32_t *info_out /* (B,) */, void *workspace,
                                       size_t workspace_bytes, int64_t Bc, void *stream);
 
