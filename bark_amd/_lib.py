@@ -24,6 +24,7 @@ BARK_ERR_ARG, BARK_ERR_TREE, BARK_ERR_CATEGORICAL, BARK_ERR_HIP, BARK_ERR_WORKSP
 MLL_INCLUDE_SCALE, MLL_INCLUDE_2PI, MLL_RHS_IDENTITY = 1, 2, 4
 SAMPLE_FULL, SAMPLE_MAX, SAMPLE_MIN = 0, 1, 2  # BARK_SAMPLE_*
 ACQ_LCB_MEAN, ACQ_LCB_MIXTURE, ACQ_EI, ACQ_PI, ACQ_MES = 0, 1, 2, 3, 4  # BARK_ACQ_*
+SCORE_HELDOUT, SCORE_LOO = 0, 1  # BARK_SCORE_*
 
 i64, vp, ci = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
 
@@ -146,6 +147,9 @@ SIGNATURES = {
     "bark_acquisition_scan_targets_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64, i64, i64]),
     "bark_acquisition_scan_targets_hip": (ci, [vp, vp, ctypes.POINTER(PackInfo), vp, i64, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64,
                                                vp, i64, ctypes.c_double, ci, ci, vp, vp, vp, vp, vp, ctypes.c_size_t, i64, vp]),
+    "bark_predictive_scores_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64, i64]),
+    "bark_predictive_scores_hip": (ci, [vp, vp, ctypes.POINTER(PackInfo), vp, i64, i64, vp, vp, vp, vp, i64, vp, ci, ci, vp, vp, vp,
+                                        vp, vp, ctypes.c_size_t, i64, vp]),
     "bark_lowrank_workspace_bytes": (ctypes.c_size_t, [i64, i64]),
     "bark_lowrank_update_hip": (ci, [vp, i64, vp, i64, ci, ci, vp, vp, vp, ctypes.c_size_t, vp]),
     "bark_lowrank_swap_eval_hip": (ci, [vp, i64, vp, i64, i64, vp, vp, vp, ctypes.c_size_t, vp]),

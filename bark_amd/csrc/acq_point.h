@@ -1,0 +1,62 @@
+// The per-point part of the leaf-space kernels that run one thread per point over the forests of a chunk (acq_scan_kernel
+// in acquire.hip, score_scan_kernel in scores.hip): the forest's table image into LDS, the point's leaf list, and the two
+// leaf-space sums.  Both kernels form mu_b and var_b from these in the same order, so they agree bit for bit.
+// LDS layout (dynamic, ACQ_TILE threads): with LDS_TABLE the forest's image ([tri + R] doubles: packed upper triangle of
+// M^-1, then w; acq_pack) in front of the tile's leaf lists ([m][ACQ_TILE] 16-bit ids, lane fastest: conflict-free);
+// otherwise only the lists, and M^-1 / w are read from global memory.
+#pragma once
+#include "common.h"
+
+namespace bark {
+
+// the image of forest b of the chunk into LDS; the caller's barriers separate it from the reads before and after
+__device__ __forceinline__ void stage_table(const double *__restrict__ tab, int b, int tri, int R, double *smem) {
+    const double *src = tab + (size_t)b * (tri + R);
+    for (int e = threadIdx.x; e < tri + R; e += ACQ_TILE) smem[e] = src[e];
+}
+
+// Leaves of point c under forest b from its one-hot code (ccodes (bc, W, cpad)), in code-bit order (tree order), into
+// idx[k * ACQ_TILE]; returns their number, which the caller clamps to m (only the first m are stored).
+__device__ __forceinline__ int point_leaves(const uint32_t *__restrict__ ccodes, int W, int cpad, int b, int c, int m, int R,
+                                            unsigned short *idx) {
+    int cnt = 0;
+    for (int w0 = 0; w0 < W; w0 += 8) {
+        uint32_t word[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) word[u] = w0 + u < W ? ccodes[((size_t)b * W + w0 + u) * cpad + c] : 0u;
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            uint32_t bits = word[u];
+            while (bits) {  // bits in increasing order: tree order
+                const int a = 32 * (w0 + u) + __builtin_ctz(bits);
+                if (cnt < m) idx[cnt * ACQ_TILE] = (unsigned short)(a < R ? a : R - 1);
+                bits &= bits - 1;
+                ++cnt;
+            }
+        }
+    }
+    return cnt;
+}
+
+// s1 = sum_i w[a_i], dg = sum_i Minv[a_i][a_i], off = sum_i ( sum_{j < i} Minv[a_j][a_i] ) over the point's cnt leaves.  A
+// wave's 64 points walk the tree pairs (j, i) in lock step, so their table reads fall into the leaves(tree j) x leaves(tree i)
+// block of M^-1: for prior-sized trees a handful of distinct addresses, which the LDS broadcasts.
+template <bool LDS_TABLE>
+__device__ __forceinline__ void point_sums(const unsigned short *idx, int cnt, const double *smem, const double *wb,
+                                           const double *Mb, int R, double &s1, double &dg, double &off) {
+    s1 = 0.0, dg = 0.0, off = 0.0;
+    for (int i = 0; i < cnt; ++i) {
+        const int ai = idx[i * ACQ_TILE];
+        s1 += wb[ai];
+        dg += LDS_TABLE ? smem[ai * (2 * R - ai - 1) / 2 + ai] : Mb[(size_t)ai * R + ai];
+        double r = 0.0;
+#pragma unroll 4
+        for (int j = 0; j < i; ++j) {
+            const int aj = idx[j * ACQ_TILE];
+            r += LDS_TABLE ? smem[aj * (2 * R - aj - 1) / 2 + ai] : Mb[(size_t)aj * R + ai];
+        }
+        off += r;
+    }
+}
+
+}  // namespace bark

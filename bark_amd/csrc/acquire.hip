@@ -16,14 +16,11 @@
 //   acq_best_kernel     reduces those (no float atomics: ties go to the lowest candidate index)
 // The order of every sum is fixed (leaves in code-bit order, targets 0 .. S-1, forests 0 .. B-1), so the result depends neither on the chunk
 // nor on the variant: the LDS and the global variant of acq_scan_kernel run the same arithmetic on the same values.
-#include "common.h"
+#include "acq_point.h"
 
 namespace bark {
 namespace {
 
-constexpr int ACQ_TILE = 256;                  // candidates per workgroup, one per thread
-constexpr size_t ACQ_LDS_MAX = 160 * 1024;     // all of a CU's LDS: one workgroup per CU
-constexpr int ACQ_MAX_TREES = 64;
 constexpr int ACQ_COND_THREADS = 1024;         // acq_condition_kernel: one workgroup per forest
 
 // Image (bc, tri + R): row a of the upper triangle of M^-1 at a (2R - a - 1) / 2 + a, i.e. entry (a, b >= a) at
@@ -147,10 +144,8 @@ __device__ __forceinline__ double acq_target_term(double mu, double var, const d
     return -(gs / (double)S);
 }
 
-// LDS_TABLE: the forest's image sits in LDS ([tri + R] doubles) in front of the tile's leaf lists ([m][ACQ_TILE] 16-bit
-// ids, lane fastest: conflict-free); otherwise only the lists do and M^-1 / w are read from global memory.  A wave's 64
-// candidates walk the tree pairs (j, i) in lock step, so their table reads fall into the leaves(tree j) x leaves(tree i)
-// block of M^-1: for prior-sized trees a handful of distinct addresses, which the LDS broadcasts.
+// LDS_TABLE: the forest's image sits in LDS in front of the tile's leaf lists; otherwise only the lists do and M^-1 / w are
+// read from global memory (acq_point.h has the layout and the per-candidate steps).
 // n: candidates of this slab (ccodes (bc, W, cpad) holds their codes), acc: the slab's part of the (3, C) sums, row stride
 // `astride`; first: this is the first chunk of forests (the sums start at zero).
 // KIND: BARK_ACQ_LCB_MEAN for both confidence bounds (three sums; kappa), or a target kind (row 0 of acc only; targets (bc, S)).
@@ -179,44 +174,14 @@ __global__ __launch_bounds__(ACQ_TILE) void acq_scan_kernel(const uint32_t *__re
     for (int b = 0; b < bc; ++b) {
         if (LDS_TABLE) {
             __syncthreads();  // the previous forest's reads are done
-            const double *src = tab + (size_t)b * (tri + R);
-            for (int e = tid; e < tri + R; e += ACQ_TILE) smem[e] = src[e];
+            stage_table(tab, b, tri, R, smem);
         }
-        int cnt = 0;
-        if (active)
-            for (int w0 = 0; w0 < W; w0 += 8) {
-                uint32_t word[8];
-#pragma unroll
-                for (int u = 0; u < 8; ++u) word[u] = w0 + u < W ? ccodes[((size_t)b * W + w0 + u) * cpad + c] : 0u;
-#pragma unroll
-                for (int u = 0; u < 8; ++u) {
-                    uint32_t bits = word[u];
-                    while (bits) {  // bits in increasing order: tree order
-                        const int a = 32 * (w0 + u) + __builtin_ctz(bits);
-                        if (cnt < m) idx[cnt * ACQ_TILE] = (unsigned short)(a < R ? a : R - 1);
-                        bits &= bits - 1;
-                        ++cnt;
-                    }
-                }
-            }
+        int cnt = active ? point_leaves(ccodes, W, cpad, b, c, m, R, idx) : 0;
         if (cnt > m) cnt = m;
         if (LDS_TABLE) __syncthreads();
         if (!active) continue;  // no barrier depends on what follows
-        const double *wb = LDS_TABLE ? smem + tri : wvec + (size_t)b * R;
-        const double *Mb = Minv + (size_t)b * R * R;
-        double s1 = 0.0, dg = 0.0, off = 0.0;
-        for (int i = 0; i < cnt; ++i) {
-            const int ai = idx[i * ACQ_TILE];
-            s1 += wb[ai];
-            dg += LDS_TABLE ? smem[ai * (2 * R - ai - 1) / 2 + ai] : Mb[(size_t)ai * R + ai];
-            double r = 0.0;
-#pragma unroll 4
-            for (int j = 0; j < i; ++j) {
-                const int aj = idx[j * ACQ_TILE];
-                r += LDS_TABLE ? smem[aj * (2 * R - aj - 1) / 2 + ai] : Mb[(size_t)aj * R + ai];
-            }
-            off += r;
-        }
+        double s1, dg, off;
+        point_sums<LDS_TABLE>(idx, cnt, smem, LDS_TABLE ? smem + tri : wvec + (size_t)b * R, Minv + (size_t)b * R * R, R, s1, dg, off);
         const double sigma2 = 1e-6 + noise[b];
         const double sc = scale[b];
         const double mu = sc / ((double)m * sigma2) * s1;
@@ -326,11 +291,6 @@ __global__ __launch_bounds__(256) void acq_best_kernel(const double *__restrict_
     }
 }
 
-size_t scan_lds_bytes(int64_t R, int64_t m, bool lds_table) {
-    const size_t lists = (size_t)m * ACQ_TILE * sizeof(unsigned short);
-    return (lds_table ? ((size_t)R * (R + 1) / 2 + R) * sizeof(double) : 0) + lists;
-}
-
 size_t acq_condition_lds_bytes(int64_t R) { return ((size_t)R + 1) * sizeof(double) + (ACQ_MAX_TREES + 2) * sizeof(int); }
 
 // the instantiation of a variant and kind; both confidence bounds share one (they differ in the finish only)
@@ -360,6 +320,10 @@ int raise_acq_lds_limits() {
 }  // namespace
 
 int64_t acq_partials(int64_t C) { return (C + 255) / 256; }
+size_t scan_lds_bytes(int64_t R, int64_t m, bool lds_table) {
+    const size_t lists = (size_t)m * ACQ_TILE * sizeof(unsigned short);
+    return (lds_table ? ((size_t)R * (R + 1) / 2 + R) * sizeof(double) : 0) + lists;
+}
 size_t acq_table_doubles(int64_t R) { return (size_t)R * (R + 1) / 2 + R; }
 
 // M^-1 of the chunk's forests conditioned on the P pending points whose codes are pcodes (bc, W, ppad)

@@ -1301,6 +1301,8 @@ struct LeafNeeds {
                               // the per-workgroup minima of the finish
     bool chain_step = false;  // noise/scale step: new_mll and the sweep's info (Bc each), K^-1 y (Bc, N)
     int64_t pending = 0;      // acquisition scan conditioned on this many pending points: their one-hot codes
+    bool scores = false;      // predictive scores at the `scan` points: tile partials of the mixture sums (tiles, 2) and of the
+                              // per-forest sums (Bc, tiles, 2)
 };
 
 // 256-byte aligned areas handed out front to back; base == nullptr: sizes only
@@ -1325,6 +1327,7 @@ struct LeafAreas {
     double *tab, *acc;           // acquisition scan
     double *part;                // (value, index) partial results: of the draws' max / min, or of the scan's finish
     int64_t *part_i;
+    double *spart;               // predictive scores: see LeafNeeds
     double *new_mll, *kinv_y;  // noise/scale step
     int32_t *sweep_info;
     size_t total;
@@ -1361,6 +1364,7 @@ LeafAreas leaf_areas(void *workspace, int64_t N, int64_t R, int64_t m, int64_t B
     a.sweep_info = cv.take<int32_t>(q.chain_step ? nb : 0);
     a.kinv_y = cv.take<double>(q.chain_step ? nb * N : 0);
     a.pcodes = cv.take<uint32_t>(nb * a.W * a.ppad);
+    a.spart = cv.take<double>(q.scores ? (nb + 1) * 2 * acq_partials(q.scan) : 0);
     a.total = cv.o;
     return a;
 }
@@ -1391,6 +1395,11 @@ LeafNeeds scan_needs(int64_t C, int64_t P) {  // the posterior's areas with the 
     LeafNeeds q = mll_needs(C < ACQ_SLAB ? C : ACQ_SLAB);
     q.scan = C;
     q.pending = P;
+    return q;
+}
+LeafNeeds scores_needs(int64_t C) {  // the scan's areas (its three sums per point hold the mixture's state) and the tile partials
+    LeafNeeds q = scan_needs(C, 0);
+    q.scores = true;
     return q;
 }
 LeafNeeds chain_step_needs() {
@@ -1511,6 +1520,42 @@ struct LeafSystem {
 };
 
 }  // namespace
+
+// Predictive scores (include/bark_hip.h, entry points and kernels in scores.hip): the scan's sequence with the points in
+// place of the candidates; the per-forest rows are finished chunk by chunk, the mixture after the last chunk.
+size_t bark::scores_workspace_bytes(int64_t N, int64_t R, int64_t m, int64_t Bc, int64_t C) {
+    return leaf_areas(nullptr, N, R, m, Bc, scores_needs(C)).total;
+}
+
+int bark::scores_run(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d,
+                     const double *y, const double *noise, const double *scale, const double *points, int64_t C,
+                     const double *y_points, int mode, int variant, double *per_forest_out, double *mixture_out,
+                     double *values_out, int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc, void *stream_) {
+    LeafSystem sys;
+    int rc = sys.open("bark_predictive_scores_hip", ctx, packed, info, X, N, d, y, noise, info_out, workspace, workspace_bytes, Bc, C,
+                      scores_needs(C), stream_);
+    if (rc) return rc;
+    const LeafAreas &a = sys.a;
+    const int tiles = (int)acq_partials(C);
+    double *mpart = a.spart, *fpart = a.spart + (size_t)2 * tiles;
+    rc = sys.for_chunks([&](int64_t c0) -> int {
+        int r = sys.factor_chunk(noise + c0, scale + c0, info_out + c0, nullptr, 0);
+        if (r || (r = sys.solve_w_minv())) return r;
+        if (variant == 1 && (r = acq_pack(a.Minv, a.w, sys.R, sys.bc, a.tab, sys.caller))) return r;
+        for (int64_t s0 = 0; s0 < C; s0 += ACQ_SLAB) {
+            const int64_t n = C - s0 < ACQ_SLAB ? C - s0 : ACQ_SLAB;
+            if ((r = sys.walk_candidates(points + (size_t)s0 * d, n))) return r;
+            r = score_scan(variant, mode, a.ccodes, sys.W, (int)bark_leaf_npad(n), (int)n, a.w, a.Minv, a.tab, sys.R, noise + c0,
+                           scale + c0, sys.m, sys.bc, info_out + c0, y_points + s0, c0 == 0, a.acc + s0, (size_t)C, fpart, tiles,
+                           (int)(s0 / ACQ_TILE), sys.caller);
+            if (r) return r;
+        }
+        if ((r = score_forests(fpart, tiles, sys.bc, per_forest_out + 2 * c0, sys.caller))) return r;
+        return sys.close_chunk();
+    });
+    if (rc) return rc;
+    return score_finish(a.acc, C, (int)sys.B, y_points, values_out, mpart, info_out, per_forest_out, mixture_out, sys.caller);
+}
 
 extern "C" {
 

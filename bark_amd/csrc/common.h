@@ -130,7 +130,12 @@ int sample_gather(const uint32_t *ccodes, int W, int cpad, int C, const double *
                   int reduce, double *f, double *red, int64_t *ridx, double *part, int64_t *part_i, hipStream_t s);
 
 // acquire.hip
+constexpr int ACQ_TILE = 256;               // points per workgroup of the scan and the score kernels, one per thread
+constexpr size_t ACQ_LDS_MAX = 160 * 1024;  // all of a CU's LDS: one workgroup per CU
+constexpr int ACQ_MAX_TREES = 64;
 int64_t acq_partials(int64_t C);
+// dynamic LDS of a scan / score launch: the tile's leaf lists and, with lds_table, the forest's image in front of them
+size_t scan_lds_bytes(int64_t R, int64_t m, bool lds_table);
 size_t acq_table_doubles(int64_t R);
 // M^-1 of the chunk's forests conditioned on the P pending points whose codes are pcodes (bc, W, ppad)
 int acq_condition(const uint32_t *pcodes, int W, int ppad, int P, double *Minv, int R, const double *noise, const double *scale,
@@ -144,6 +149,26 @@ int acq_scan(int variant, int kind, const uint32_t *ccodes, int W, int cpad, int
              int S, int first, double *acc, size_t astride, hipStream_t s);
 int acq_finish(const double *acc, int64_t C, int B, double kappa, int kind, const int64_t *skip, int n_skip, double *acq_out,
                double *part_v, int64_t *part_i, const int32_t *info, double *best, int64_t *best_i, hipStream_t s);
+
+// scores.hip (entry points; their host driver is LeafSystem's, chol.hip)
+// n points of one slab, whose first tile is tile0 of the call's `tiles`, against the bc forests of the chunk: the mixture's
+// running state per point in the slab's part of acc (3, C; row stride astride) and one partial pair per (forest, tile) in
+// fpart (bc, tiles, 2).  variant as acq_scan; mode: BARK_SCORE_*; info: the chunk's sweep status; yp: the slab's targets
+int score_scan(int variant, int mode, const uint32_t *ccodes, int W, int cpad, int n, const double *wvec, const double *Minv,
+               const double *tab, int R, const double *noise, const double *scale, int m, int bc, const int32_t *info,
+               const double *yp, int first, double *acc, size_t astride, double *fpart, int tiles, int tile0, hipStream_t s);
+// rows (bc, 2) of per_forest_out from fpart, the tiles in index order
+int score_forests(const double *fpart, int tiles, int bc, double *rows, hipStream_t s);
+// the per-point mixture terms (values_out (2, C) or null), their sums through mpart (tiles, 2), and NaN wherever info says so
+int score_finish(const double *acc, int64_t C, int B, const double *yp, double *values_out, double *mpart, const int32_t *info,
+                 double *per_forest_out, double *mixture_out, hipStream_t s);
+// chol.hip: what bark_predictive_scores_workspace_bytes / bark_predictive_scores_hip do once the arguments of their own are
+// checked (variant resolved by bark_acquisition_plan)
+size_t scores_workspace_bytes(int64_t N, int64_t R, int64_t m, int64_t Bc, int64_t C);
+int scores_run(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d, const double *y,
+               const double *noise, const double *scale, const double *points, int64_t C, const double *y_points, int mode,
+               int variant, double *per_forest_out, double *mixture_out, double *values_out, int32_t *info_out, void *workspace,
+               size_t workspace_bytes, int64_t Bc, void *stream);
 
 constexpr size_t STAGE_BYTES = 64 * 1024;  // bark_ctx::stage_host / stage_dev
 constexpr int NODE_BYTES = 26;          // forest.py:8-19, packed

@@ -453,6 +453,49 @@ int bark_acquisition_scan_targets_hip(bark_ctx *ctx, const void *packed, const b
                                       size_t workspace_bytes, int64_t Bc, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Predictive scores: how well the forest samples predict targets y_c at C points, in the same leaf space and again without
+ * (B, C) arrays — what the reference's bark.utils.metrics (gaussian_log_likelihood, nlpd, mse; metrics.py:5-39) gives when fed
+ * forest_predict's output, per forest and for the equally weighted mixture of the forests.  With
+ *   l_bc = log N(y_c; mu_bc, var_bc) = -0.5 log(2 pi var_bc) - 0.5 (y_c - mu_bc)^2 / var_bc:
+ *   per_forest_out[b] = ( sum_c l_bc,  sum_c (y_c - mu_bc)^2 )                                     (B, 2)
+ *   mixture_out       = ( sum_c log( (1/B) sum_b exp l_bc ),  sum_c (y_c - (1/B) sum_b mu_bc)^2 )  (2,)
+ *   values_out        = the two per-point terms of mixture_out, (2, C), or NULL
+ * so the reference's nlpd column of forest b is -per_forest_out[b][0] / C.
+ * mode = BARK_SCORE_HELDOUT: points (C, d) are held-out inputs; mu_bc and var_bc are those of forest_predict(diag=True), i.e.
+ *   the scan's mu_b(x) and var_b(x) above, formed the same way (var is the latent variance: no noise is added).
+ * mode = BARK_SCORE_LOO: points must be the training inputs X and y_points the training targets y (C == N is checked; the
+ *   contents are the caller's responsibility).  (mu_bi, var_bi) is the leave-one-out predictive of observation i: with
+ *   K_s = scale K + s2 I the matrix the leaf-space MLL factors (s2 = 1e-6 + noise), alpha = K_s^-1 y, kappa_i = [K_s^-1]_ii,
+ *       mu_i = y_i - alpha_i / kappa_i,   var_i = 1 / kappa_i.
+ *   From K_s^-1 = (I - c Z M^-1 Z') / s2 (Woodbury, c = scale / (m s2), M = I_R + c Z'Z, w = M^-1 Z'y) and z_i the one-hot
+ *   row of point i:   kappa_i = (1 - c q_i) / s2,  q_i = z_i' M^-1 z_i;   alpha_i = (y_i - c z_i'w) / s2,  z_i'w = sum_k w[a_k],
+ *   hence             mu_i = y_i - (y_i - c sum_k w[a_k]) / (1 - c q_i),   var_i = s2 / (1 - c q_i):
+ *   the two per-point sums of the scan, evaluated at the training points; no N x N matrix is formed.  var_i is the variance of
+ *   the observation (it contains s2), unlike the held-out latent variance.
+ * Order (part of the contract): a point's leaves in code-bit order; the log-sum-exp over forests is the online recurrence
+ *   top = max(mx, l), se = se exp(mx - top) + exp(l - top), mx = top  (mx = -inf, se = 0 before forest 0),  result mx + log(se / B),
+ * over b = 0 .. B-1 across chunks; sums over points run by a fixed tree within each tile of 256 points (xor butterfly in a
+ * wave, then waves 0 .. 3) and over the tiles in index order.  No float atomics: the results depend neither on Bc nor on the
+ * variant, bit for bit.
+ * A forest with info_out[b] != 0 leaves NaN in its row of per_forest_out and in both entries of mixture_out; the other rows are
+ * what a call without that forest gives.  A NaN in y_points propagates into every sum its point enters.  var <= 0 is not
+ * clamped: the logarithm then yields NaN or an infinity, which propagates likewise (a posterior variance is positive unless
+ * rounding wins, as noise -> 0).
+ * variant and its plan, and the limits refused with BARK_ERR_ARG before any launch, are the scan's: m <= 64, R <= 8192,
+ * 1 <= C <= 2^24, variant = 1 where the LDS does not hold the table; also an unknown mode and, for BARK_SCORE_LOO, C != N.
+ * The call only enqueues.  Extra memory: the scan's, plus 2 (Bc + 1) ceil(C / 256) doubles of tile partials.
+ * ------------------------------------------------------------------------------------- */
+#define BARK_SCORE_HELDOUT 0
+#define BARK_SCORE_LOO 1
+size_t bark_predictive_scores_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t Bc, int64_t C);
+int bark_predictive_scores_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N,
+                               int64_t d, const double *y, const double *noise, const double *scale, const double *points,
+                               int64_t C, const double *y_points /* (C,) */, int mode, int variant,
+                               double *per_forest_out /* (B, 2) */, double *mixture_out /* 2 */,
+                               double *values_out /* (2, C) or NULL */, int32_t *info_out /* (B,) */, void *workspace,
+                               size_t workspace_bytes, int64_t Bc, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Woodbury / determinant-lemma updates — quick_inverse.py:13-33 (the per-tree step of the sampler,
  * bark_sampler.py:233-257).  With mul = -1 if `subtract` else +1:
  *   K_out         = K_inv - K_inv U (mul I + U' K_inv U)^-1 U' K_inv          (low_rank_inv_update)
