@@ -221,8 +221,9 @@ def decide(delta, log_q, log_u) -> int:
 class Case(NamedTuple):
     N: int
     nc: int
-    init: tuple  # leaves of the m initial trees
-    steps: tuple  # (tree index, kind, leaves): kind "cat" caterpillar, "dead" unreached_tree, "g3" a golden tree
+    init: tuple  # the m initial trees: a leaf count (a caterpillar) or (kind, leaves) with the kinds of `steps`
+    steps: tuple  # (tree index, kind, leaves[, log_u]): kind "cat" caterpillar, "dead" unreached_tree, "g3" a golden tree; log_u,
+    #               one number or one per chain (None: the random draw), replaces the draw: TAKE accepts, REFUSE rejects
     capacity: int
     lcap: int
     noise: float  # centre of the chains' noise levels (>= 1e-2)
@@ -231,6 +232,7 @@ class Case(NamedTuple):
     why: str
 
 
+TAKE, REFUSE = -1e3, 1.0  # forced log_u: below every finite log_alpha of the table / positive, which the rule never accepts
 _EDGE = ((0, "cat", 5), (1, "cat", 1), (2, "cat", 4), (0, "cat", 2), (1, "dead", 3))
 CASES = {
     "n3": Case(3, 1, (1, 2), ((0, "cat", 2), (1, "cat", 1), (0, "cat", 3)), 8, 4, 0.1, 0, True, "fewer points than lanes, m = 2"),
@@ -245,6 +247,31 @@ CASES = {
                     "mixed cat / int / cont golden forests of 50 trees"),
     "n4097": Case(4097, 4, (3, 5, 2, 4), ((0, "cat", 6), (1, "cat", 2), (0, "cat", 3)), 32, 8, 1.0, 0, False,
                   "65 plane words; the conditioning of a large N"),
+    # wide trees and full slot capacity.  Every initial tree of the m = 64 cases has 9 leaves: 576 active slots, more than the
+    # 512 threads of a workgroup.  Steps with a forced log_u are the ones tests/test_leafchain_reference_cpu.py
+    # (test_table_contains_the_wide_edges) needs taken or refused; the others keep their random draw.
+    "m64_cap1024": Case(600, 2, (9,) * 64, (
+        (0, "cat", 32, TAKE),  # 9 -> 32: pops 23 slots
+        (0, "cat", 32, (TAKE, REFUSE)),  # 32 -> 32 taken by chain 0; chain 1 refuses a 32-leaf proposal (inT reset, nothing written)
+        (1, "cat", 23),  # 9 -> 23: steps 4 and 6 one entry past a pass of the workgroup
+        (63, "cat", 12, TAKE),  # the last tree
+        (2, "dead", 32, TAKE),  # 31 leaves no point reaches
+        (0, "cat", 1, TAKE),  # 32 -> 1: pushes 31 slots
+        (5, "cat", 32, TAKE),  # 9 -> 32: pops 23 of the pushed slots, last pushed first
+        (2, "cat", 5),  # pushes 27 slots with empty planes
+        # a 32-leaf proposal taken last: every accepted step computes q' afresh, so only the last one's v_O'Qv — at 32 leaves
+        # the entry of step 6 that falls into the workgroup's third pass — reaches the scalars the sweep returns
+        (63, "cat", 32, (TAKE, None))), 1024, 32, 0.1, 0, True,
+        "m = 64 trees, 1024 slots, 32-leaf trees on both sides, pushes and pops of tens of slots"),
+    # the table builder's worst case: 576 + (32 - 9) + (20 - 9) + (30 - 9) + (23 - 9) = 645 slots, odd; chain 0 takes every
+    # growing step and runs the free stack empty before tree 3 shrinks
+    "m64_tight": Case(600, 2, (9,) * 64, (
+        (3, "cat", 32, TAKE), (63, "cat", 20, (TAKE, None)), (10, "cat", 30, (TAKE, None)), (1, "cat", 23, (TAKE, None)),
+        (3, "cat", 1, TAKE), (10, "cat", 30)), 645, 32, 0.1, 3, True,
+        "the capacity is the sweep's worst case exactly, odd and above 512; no free slot left in chain 0 after step 3"),
+    "odd67": Case(130, 2, (5, ("dead", 9), 7, 11), ((0, "cat", 12), (1, "cat", 3), (2, "cat", 13), (3, "cat", 2), (1, "cat", 10)),
+                  67, 13, 0.1, 0, True, "ragged tails of the lane- and wave-strided loops (67 slots), r from 9 to 13 = lcap, "
+                  "empty-plane slots below active ones at init"),
 }
 
 
@@ -288,10 +315,10 @@ def make_inputs(name) -> Inputs:
         noise = np.maximum(noise, 0.05)
     else:
         X, y, _, ft = synthetic.unit_cube_problem(case.N, D, seed=1000 * case.N + case.seed)
-        forests = np.stack([np.stack([lr.caterpillar_tree(k, (b + t) % D) for t, k in enumerate(case.init)]) for b in range(case.nc)])
         kinds = {"cat": lr.caterpillar_tree, "dead": unreached_tree}
-        new = np.stack([np.stack([kinds[kind](k, (b + 2 * t + 1) % D) for t, (_, kind, k) in enumerate(case.steps)])
-                        for b in range(case.nc)])
+        init = [k if isinstance(k, tuple) else ("cat", k) for k in case.init]
+        forests = np.stack([np.stack([kinds[kind](k, (b + t) % D) for t, (kind, k) in enumerate(init)]) for b in range(case.nc)])
+        new = np.stack([np.stack([kinds[s[1]](s[2], (b + 2 * t + 1) % D) for t, s in enumerate(case.steps)]) for b in range(case.nc)])
         capacity = case.capacity
         noise = rng.uniform(0.8 * case.noise, 1.6 * case.noise, case.nc)
         scale = rng.uniform(0.7, 1.4, case.nc)
@@ -303,6 +330,11 @@ def make_inputs(name) -> Inputs:
         old[:, t] = new[:, prev[-1]] if prev else forests[:, tidx[t]]
     log_q = rng.normal(0.0, 0.5, size=(case.nc, steps))
     log_u = np.log(rng.uniform(size=(case.nc, steps)))
+    for t, s in enumerate(case.steps):
+        if len(s) > 3:  # a forced log_u, drawn over: the stream of the random ones is the same with and without it
+            for b, forced in enumerate(np.broadcast_to(np.array(s[3], dtype=object), (case.nc,))):
+                if forced is not None:
+                    log_u[b, t] = forced
     return Inputs(X, y, ft, forests, old, new, tidx, noise, scale, log_q, log_u, capacity, case.lcap)
 
 
@@ -313,6 +345,17 @@ class Trajectory(NamedTuple):
     logdet: np.ndarray
     chains: list  # the RefChain of every chain (None on the dense route)
     final: np.ndarray  # (nc, m, node_limit) forests after the sweep
+    init_active: list = None  # per chain the slots with a non-empty plane at init (leaf route)
+    log: list = None  # per chain, per step: StepLog (leaf route)
+
+
+class StepLog(NamedTuple):
+    r_old: int
+    r_new: int
+    accepted: bool
+    popped: tuple  # slots the swap took off RefChain's free stack, in the order taken
+    pushed: tuple  # slots it put on the stack, in the order put
+    free_after: int  # depth of the stack after the step
 
 
 def leaf_sweep(inp: Inputs, dtype=np.float64, symmetric=True, chains=None) -> Trajectory:
@@ -320,19 +363,28 @@ def leaf_sweep(inp: Inputs, dtype=np.float64, symmetric=True, chains=None) -> Tr
     mask, margin = np.zeros((nc, steps), dtype=np.int32), np.full((nc, steps), np.inf)
     quad, logdet, out = np.zeros(nc), np.zeros(nc), [None] * nc
     final = inp.forests.copy()
+    active, log = [None] * nc, [None] * nc
     for b in (range(nc) if chains is None else chains):
         ch = RefChain(inp.forests[b], inp.noise[b], inp.scale[b], inp.X, inp.y, inp.ft, inp.capacity, dtype, symmetric)
+        active[b], log[b] = np.flatnonzero(ch.Z.any(axis=0)), []
         for t in range(steps):
-            delta, commit = ch.propose(int(inp.tree_index[t]), inp.new[b, t])
+            k = int(inp.tree_index[t])
+            held, stack = list(ch.slots[k]), list(ch.free)
+            delta, commit = ch.propose(k, inp.new[b, t])
             if np.isfinite(inp.log_q[b, t] + delta) and np.isfinite(inp.log_u[b, t]):
                 margin[b, t] = abs(inp.log_u[b, t] - (inp.log_q[b, t] + delta))
             mask[b, t] = decide(delta, inp.log_q[b, t], inp.log_u[b, t])
             if mask[b, t]:
                 commit()
                 final[b, inp.tree_index[t]] = inp.new[b, t]
+            kept = 0  # a swap pops or pushes, never both: the stack below `kept` is untouched
+            while kept < min(len(stack), len(ch.free)) and stack[kept] == ch.free[kept]:
+                kept += 1
+            log[b].append(StepLog(len(held), len(ch.slots[k]) if mask[b, t] else len(leaf_order(inp.new[b, t])), bool(mask[b, t]),
+                                  tuple(stack[kept:][::-1]), tuple(ch.free[kept:]), len(ch.free)))
         q, ld = ch.state()
         quad[b], logdet[b], out[b] = float(q), float(ld), ch
-    return Trajectory(mask, margin, quad, logdet, out, final)
+    return Trajectory(mask, margin, quad, logdet, out, final, active, log)
 
 
 def dense_sweep(inp: Inputs, chains=None) -> Trajectory:

@@ -4,7 +4,16 @@ the final forests.  tests/test_leafchain_reference_cpu.py holds every case to a 
 must be identical, not close.  Bars: the project's scalar bar (rtol 1e-9 / atol 1e-9) and matrix bar (rtol 1e-9 / atol 1e-11);
 for case n4097 the matrix bar is 100 x the host reference's own float64-against-longdouble deviation.
 
-Not tested: the -1 latch of a non-positive pivot in P_TT or S, which no valid forest reaches."""
+The cases m64_cap1024, m64_tight and odd67 take the kernel to the corners of its limits (64 trees, 32 leaves per tree, 1024
+slots): small inverses of 23 and 32 rows, steps 4 and 6 past one pass of the workgroup, a 63-node tree in LDS, capacities above
+the 512 threads and off every multiple of 8, more than 512 active slots with gaps in `lc_build_inverse`, swaps of tree 63, and a
+free stack that is pushed 31 deep and popped again, so that the bit-for-bit comparison of slot map and stack with the host
+reference says something.  tests/test_leafchain_reference_cpu.py (test_table_contains_the_wide_edges) holds the table to
+containing these steps, taken or refused as needed.  ChainBatch accepts every step of the table (r_old + r_new <= 64), so every
+case is compared with the launches route too.  Chain isolation, the noise / scale step and the guard bands run on one small
+case and on m64_cap1024.
+
+Not tested: the -1 latch of a non-positive pivot in P_TT or S, which no valid forest reaches; N above 4097."""
 import numpy as np
 import pytest
 
@@ -94,7 +103,8 @@ def test_cases(G, name):
     case = lc.CASES[name]
     inp, want = ref(name)
     dev = batch(G, inp)
-    assert dev.sweep_plan()["chain_bytes"] < 8 * case.N * case.N or case.N < 300
+    # the state is smaller than an N x N inverse; the wide cases hold more slots than points (P alone is 8 capacity^2 bytes)
+    assert dev.sweep_plan()["chain_bytes"] < 8 * case.N * case.N or case.N < 300 or inp.capacity >= case.N
     mask = sweep(dev, inp)
     assert np.array_equal(mask, want.mask == 1), (mask, want.mask)
     mask_l, launches = dense_launches(G, inp)
@@ -151,9 +161,14 @@ def test_g11_replay(G):
         check_free_slots(cb, b)
 
 
-def test_repeatable_and_chains_isolated(G):
+WIDE = ["n65", "m64_cap1024"]  # one small case and the full box: two chains each
+
+
+@pytest.mark.parametrize("name", WIDE)
+def test_repeatable_and_chains_isolated(G, name):
     torch = G.torch
-    inp, want = ref("n65")
+    inp, want = ref(name)
+    m = inp.forests.shape[1]
     a, b2 = batch(G, inp), batch(G, inp)
     assert torch.equal(a.state, b2.state) and np.array_equal(a.quad, b2.quad)
     ma, mb = sweep(a, inp), sweep(b2, inp)
@@ -170,7 +185,7 @@ def test_repeatable_and_chains_isolated(G):
     before = c.state.clone()
     lu = inp.log_u.copy()
     lu[1] = 1.0  # log_u > 0: never accepted
-    m1 = c.sweep_trees(inp.old, inp.new, inp.log_q, lu, inp.X, inp.ft, inp.scale, 3, tree_index=inp.tree_index)
+    m1 = c.sweep_trees(inp.old, inp.new, inp.log_q, lu, inp.X, inp.ft, inp.scale, m, tree_index=inp.tree_index)
     assert not m1[1].any() and np.array_equal(m1[0], ma[0])
     assert torch.equal(c.state[stride:], before[stride:]) and c.quad[1] == batch(G, inp).quad[1]
 
@@ -180,7 +195,7 @@ def test_nan_rule(G):
     lq, lu = inp.log_q.copy(), inp.log_u.copy()
     lu[0, 0], lq[1, 0] = np.nan, np.nan
     dev = batch(G, inp)
-    mask = dev.sweep_trees(inp.old, inp.new, lq, lu, inp.X, inp.ft, inp.scale, 3, tree_index=inp.tree_index)
+    mask = dev.sweep_trees(inp.old, inp.new, lq, lu, inp.X, inp.ft, inp.scale, inp.forests.shape[1], tree_index=inp.tree_index)
     assert not mask[0, 0], "a NaN log_u was accepted"
     assert not mask[1, 0], "a NaN log_q_prior was accepted"
     chk = lc.leaf_sweep(inp._replace(log_q=lq, log_u=lu))
@@ -190,6 +205,7 @@ def test_nan_rule(G):
 def test_refusals(G):
     torch = G.torch
     inp, _ = ref("n129")  # the worst case of this sweep needs 24 slots
+    m = inp.forests.shape[1]
     with pytest.raises(ValueError, match="capacity"):
         sweep(batch(G, inp, capacity=23), inp)
     cb = batch(G, inp)
@@ -197,33 +213,45 @@ def test_refusals(G):
     big = inp.new.copy()
     big[1, 2] = lr.caterpillar_tree(9, 0)  # lcap + 1 leaves
     with pytest.raises(ValueError, match="leaves"):
-        cb.sweep_trees(inp.old, big, inp.log_q, inp.log_u, inp.X, inp.ft, inp.scale, 3, tree_index=inp.tree_index)
+        cb.sweep_trees(inp.old, big, inp.log_q, inp.log_u, inp.X, inp.ft, inp.scale, m, tree_index=inp.tree_index)
     wrong = inp.old.copy()
     wrong[0, 0] = lr.caterpillar_tree(5, 0)  # not the tree the chain holds
     with pytest.raises(ValueError, match="old_trees"):
-        cb.sweep_trees(wrong, inp.new, inp.log_q, inp.log_u, inp.X, inp.ft, inp.scale, 3, tree_index=inp.tree_index)
+        cb.sweep_trees(wrong, inp.new, inp.log_q, inp.log_u, inp.X, inp.ft, inp.scale, m, tree_index=inp.tree_index)
     with pytest.raises(ValueError):
-        cb.sweep_trees(inp.old, inp.new, inp.log_q, inp.log_u, inp.X, inp.ft, inp.scale, 3, tree_index=[0, 3, 1, 1])
+        cb.sweep_trees(inp.old, inp.new, inp.log_q, inp.log_u, inp.X, inp.ft, inp.scale, m, tree_index=[0, m, 1, 1])
     assert torch.equal(cb.state, before)
     with pytest.raises(ValueError):
         G.fit.LeafChainBatch.from_forests(np.repeat(inp.forests[:1], 65, axis=0), 0.1, 1.0, inp.X, inp.y, inp.ft)
     with pytest.raises(ValueError, match="lcap"):
         G.fit.LeafChainBatch.from_forests(inp.forests, inp.noise, inp.scale, inp.X, inp.y, inp.ft, lcap=7)
+    with pytest.raises(ValueError, match="trees"):  # 65 trees
+        G.fit.LeafChainBatch.from_forests(np.repeat(inp.forests[:, :1], 65, axis=1), inp.noise, inp.scale, inp.X, inp.y, inp.ft)
+    tight = lc.make_inputs("m64_tight")  # its capacity is the sweep's worst case exactly: one slot less is refused before any launch
+    cb = batch(G, tight, capacity=tight.capacity - 1)
+    before = cb.state.clone()
+    with pytest.raises(ValueError, match="capacity"):
+        sweep(cb, tight)
+    assert torch.equal(cb.state, before)
     one = torch.zeros(64, dtype=torch.float64, device="cuda")
     p = G.L.ptr(one)
     rc = G.lib.bark_leafchain_sweep_hip(G.L.ctx(), p, 4, 1025, 2, 4, 1, 1, p, p, p, 1, p, p, p, p, p, p, 1 << 30, G.L.stream_ptr())
     assert rc == G.L.BARK_ERR_ARG and b"slots" in G.lib.bark_last_error() and not bool(one.any())
 
 
-def test_noise_scale_step(G):
-    """Accepted, rejected and a negative scale (-1 -> LinAlgError, nothing written), against ChainBatch.step_noise_scale."""
-    inp, want = ref("n65")
+@pytest.mark.parametrize("name", WIDE)
+def test_noise_scale_step(G, name):
+    """Accepted, rejected and a negative scale (-1 -> LinAlgError, nothing written), against ChainBatch.step_noise_scale; at
+    m64_cap1024 `lc_build_inverse` eliminates 576 active slots, more than the workgroup has threads.  The proposals' MLL
+    differences, which only place log_u half a unit to either side of the decision, are the oracle's."""
+    inp, want = ref(name)
+    m = inp.forests.shape[1]
     dev = batch(G, inp)
     dense = G.fit.ChainBatch.from_forests(inp.forests, inp.noise, inp.scale, inp.X, inp.y, inp.ft)
     assert lr.used(dev.mll, dense.mll, lr.SCALAR_RTOL, lr.SCALAR_ATOL) <= 1.0
     nn, ns = inp.noise * np.array([1.3, 0.8]), inp.scale * np.array([0.9, 1.2])
-    deltas = [want_chain.propose_noise_scale(nn[b], ns[b])[0] for b, want_chain in
-              enumerate(lc.RefChain(inp.forests[b], inp.noise[b], inp.scale[b], inp.X, inp.y, inp.ft, inp.capacity) for b in range(2))]
+    mll = lambda noise, scale: G.orc.batched_mll(inp.forests, noise, scale, inp.X, inp.y, inp.ft, include_scale=True, include_2pi=False)
+    deltas = mll(nn, ns) - mll(inp.noise, inp.scale)
     lq = np.zeros(2)
     # chain 0 accepted; chain 1 rejected by the comparison itself where a non-positive log_u allows it
     lu = np.array([min(deltas[0], 0.0) - 0.5, deltas[1] + 0.5 if deltas[1] < -0.6 else 0.5])
@@ -241,7 +269,7 @@ def test_noise_scale_step(G):
     now = lc.dense_P(inp.forests[0], nn[0], ns[0], inp.X, inp.ft, inp.capacity)
     assert lr.used(dev.export()["P"][0], now, lr.MAT_RTOL, lr.MAT_ATOL) <= 1.0
     # the sweep goes on from the accepted values
-    mask2 = dev.sweep_trees(inp.old, inp.new, inp.log_q, np.full_like(inp.log_u, 1.0), inp.X, inp.ft, dev.scale, 3, tree_index=inp.tree_index)
+    mask2 = dev.sweep_trees(inp.old, inp.new, inp.log_q, np.full_like(inp.log_u, 1.0), inp.X, inp.ft, dev.scale, m, tree_index=inp.tree_index)
     assert not mask2.any()
     before = dev.state.clone()
     quad = dev.quad.copy()
@@ -252,11 +280,13 @@ def test_noise_scale_step(G):
     assert not m3.any() and G.torch.equal(dev.state, before)
 
 
-def test_guard_bands_and_graph_capture(G):
+@pytest.mark.parametrize("name", WIDE)
+def test_guard_bands_and_graph_capture(G, name):
     """The state block and the workspace sit between bands that stay intact, and the sweep — one enqueued kernel — is captured
-    in a graph: the capture runs nothing, one replay gives the eager call's bits."""
+    in a graph: the capture runs nothing, one replay gives the eager call's bits.  At m64_cap1024 the workspace matrices run at
+    1024 x 32 and P and the scratch inverse at 1024 x 1024, the largest the layout allows."""
     torch = G.torch
-    inp, want = ref("n65")
+    inp, want = ref(name)
     cb = batch(G, inp)
     start, mstate0 = cb.state.clone(), cb._mstate.clone()
     band = 4096
@@ -275,7 +305,8 @@ def test_guard_bands_and_graph_capture(G):
     cb.state.copy_(start)
     cb._mstate.copy_(mstate0)
     cb.nleaves = batch(G, inp).nleaves
-    enqueue, accept, tidx, r_new, ft = cb._prepare_sweep(inp.old, inp.new, inp.log_q, inp.log_u, inp.X, inp.ft, inp.scale, 3, inp.tree_index)
+    enqueue, accept, tidx, r_new, ft = cb._prepare_sweep(inp.old, inp.new, inp.log_q, inp.log_u, inp.X, inp.ft, inp.scale, inp.forests.shape[1],
+                                                             inp.tree_index)
     accept.zero_()
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()

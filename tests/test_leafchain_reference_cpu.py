@@ -49,6 +49,61 @@ def test_case_conditions(name):
         assert dev <= lc.N4097_P_DEVIATION
 
 
+def test_table_contains_the_wide_edges():
+    """The edges the wide cases exist for are really in the table — conditions on the host reference's trajectory (taken steps,
+    RefChain's free stack), not measurements: without them tests/test_gpu_leafchain.py would pass without having run them."""
+    wide, tight, odd = (runs(name)[1] for name in ("m64_cap1024", "m64_tight", "odd67"))
+    steps = lc.CASES["m64_cap1024"].steps
+    every = [(steps[t], s) for chain in wide.log for t, s in enumerate(chain)]
+    taken = [(step, s) for step, s in every if s.accepted]
+    assert any(s.r_old == 32 and s.r_new == 32 for _, s in taken), "no accepted 32 -> 32 swap"
+    assert any(s.r_new >= 23 and s.r_old <= 9 for _, s in taken), "no accepted swap from <= 9 to >= 23 leaves"
+    assert any(step[0] == 63 for step, _ in taken), "no accepted swap of tree 63"
+    assert any(step[1] == "dead" and s.r_new == 32 for step, s in taken), "no accepted 32-leaf proposal of unreached leaves"
+    assert any(s.r_new == 32 and not s.accepted for _, s in every), "no rejected 32-leaf proposal"
+    assert any(len(s.popped) >= 23 for _, s in taken) and any(len(s.pushed) == 31 for _, s in taken)
+    # an accepted step computes q' afresh, so the returned scalars see only the last one: it must be a 32-leaf proposal somewhere
+    assert any([s.r_new for s in chain if s.accepted][-1] == 32 for chain in wide.log), "no chain ends on an accepted 32-leaf swap"
+
+    def pops_what_was_pushed(chain):
+        for t, s in enumerate(chain):
+            if s.accepted and (s.r_old, s.r_new) == (32, 1):
+                assert len(s.pushed) == 31
+                for later in chain[t + 1:]:
+                    back = [x for x in later.popped if x in s.pushed]
+                    if later.accepted and back:
+                        # last pushed, first popped: not the ascending order the stack gives after init
+                        assert back == [x for x in s.pushed[::-1] if x in back] and back != sorted(back)
+                        return True
+        return False
+
+    assert any(pops_what_was_pushed(chain) for chain in wide.log), "no accepted 32 -> 1 swap whose slots a later swap pops"
+    for traj in (wide, tight):
+        assert all(len(a) > 512 for a in traj.init_active), [len(a) for a in traj.init_active]
+    for a in odd.init_active:  # the unreached leaves of the initial forest sit between active slots
+        assert len(set(range(int(a.max()))) - set(a.tolist())) > 0, "odd67: no empty-plane slot below an active one"
+    # m64_tight: the capacity is the worst case of the sweep over the accept masks exactly, odd, above the workgroup's 512
+    # threads, and one chain really uses all of it
+    case = lc.CASES["m64_tight"]
+    peak = [k if isinstance(k, int) else k[1] for k in case.init]
+    for step in case.steps:
+        peak[step[0]] = max(peak[step[0]], step[2])
+    assert sum(peak) == case.capacity and case.capacity % 2 == 1 and case.capacity > 512
+    assert any(s.free_after == 0 for chain in tight.log for s in chain), "m64_tight never runs the free stack empty"
+    assert lc.CASES["m64_cap1024"].capacity == 1024 and lc.CASES["odd67"].capacity % 8 != 0
+
+
+def test_tight_capacity_is_the_table_builders_bound(L):
+    """The library's table builder takes m64_tight at its capacity and refuses it with one slot less."""
+    case = lc.CASES["m64_tight"]
+    nleaves = np.tile(np.array([k if isinstance(k, int) else k[1] for k in case.init]), (case.nc, 1))
+    r_new = np.tile(np.array([s[2] for s in case.steps])[:, None], (1, case.nc))
+    tidx = [s[0] for s in case.steps]
+    assert build_table(L, tidx, r_new, nleaves, case.lcap, case.capacity, stride=63)[0] == 0
+    rc, _, msg = build_table(L, tidx, r_new, nleaves, case.lcap, case.capacity - 1, stride=63)
+    assert rc == L.BARK_ERR_ARG and "capacity" in msg
+
+
 def test_g11_trajectory_passes_the_precheck():
     """The reference sampler's recorded steps (g11: N = 48, 2 chains, 3 steps of 8 trees + a noise / scale proposal) are a GPU
     case: float64 and longdouble take the recorded decisions with a margin far above 1e-6 and reproduce the recorded MLL."""
