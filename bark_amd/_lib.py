@@ -115,6 +115,9 @@ SIGNATURES = {
                                       ctypes.c_size_t, vp]),
     "bark_leafchain_noise_scale_hip": (ci, [vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, vp]),
     "bark_leafchain_export_hip": (ci, [vp, vp, i64, i64, i64, i64, i64, vp, vp, vp, vp]),
+    "bark_tree_proposals_query": (ci, [i64, i64, i64, i64, i64, vp]),
+    "bark_tree_proposals_hip": (ci, [vp, vp, i64, i64, i64, vp, vp, i64, vp, ctypes.c_uint64, i64, vp, vp, vp, vp, vp]),
+    "bark_tree_proposals_commit_hip": (ci, [vp, vp, vp, vp, i64, i64, i64, i64, vp]),
     "bark_noise_scale_step_chains_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64]),
     "bark_noise_scale_step_chains_hip": (ci, [vp, vp, i64, i64, vp, ctypes.POINTER(PackInfo), vp, i64, vp, vp, vp, vp, vp, vp,
                                               vp, vp, ctypes.c_size_t, vp]),

@@ -462,6 +462,7 @@ class ChainBatch:
         acc, self.quad, self.logdet = _chains.read_decisions(accept, state)
         self._pending = None
         self.last_accept = acc.T.copy()
+        self.last_accept_device = accept  # (steps, chains) int32, as the device wrote it: the sampler's commit reads it there
         _raise_on_categorical_fault(ft)
         if (acc < 0).any():
             raise np.linalg.LinAlgError("Singular matrix in a tree-swap update")

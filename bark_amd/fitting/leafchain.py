@@ -188,6 +188,7 @@ class LeafChainBatch:
             took = acc[t] > 0
             self.nleaves[took, tidx[t]] = r_new[t, took]
         self.last_accept = acc.T.copy()
+        self.last_accept_device = accept  # (steps, chains) int32, as the device wrote it: the sampler's commit reads it there
         _raise_on_categorical_fault(ft)
         if (acc < 0).any():
             raise np.linalg.LinAlgError("non-positive pivot in a leaf-space tree swap")

@@ -701,6 +701,46 @@ int bark_leafchain_noise_scale_hip(bark_ctx *ctx, void *state, int64_t N, int64_
 int bark_leafchain_export_hip(bark_ctx *ctx, const void *state, int64_t N, int64_t Rcap, int64_t m, int64_t lcap, int64_t nc,
                               double *P_out, double *v_out, int32_t *nleaves_out, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Tree proposals — tree_proposals.py:187-256 (get_tree_proposal) for every (chain, tree) of a sweep in ONE launch, and the
+ * commit of the accepted ones.  Forests are the reference's packed 26-byte records, (nc, m, L), in DEVICE memory.
+ *   new_nodes    (nc, m, L) records: nodes.copy() with exactly the records grow / prune / change assign
+ *   log_q_prior  (nc, m) fp64: tree_q_ratio + tree_prior_ratio; -inf for a rejected proposal (new tree = old tree)
+ *   log_u        (nc, m) fp64: log of the uniform of bark_sampler.py:259
+ *   detail       (nc, m, 4) int32: kind (0 grow, 1 prune, 2 change), node (-1: none), feature (-1: none), status
+ *   status       0 valid | 1 no valid node | 2 invalid discrete split | 3 fewer than two inactive slots | 4 a grow would
+ *                exceed max_leaves.  3 and 4 are rejected proposals (the reference raises OverflowError for 3).
+ * Draws: Philox4x32-10, key = (seed low word, seed high word), counter = (chain_offset + chain, tree_offset + tree, sweep,
+ * block); words (0,1) and (2,3) of a block are one 64-bit draw each, low word first, u = (x >> 11) * 2^-53:
+ *   block 0: kind, node;  block 1: feature, threshold or mask;  block 2: accept.
+ *   kind = searchsorted(cumsum(weights / sum), u);  node = valid[floor(u n)];  feature = floor(u d);
+ *   categorical: 1 + floor(u (2^k - 2)) spread over the k set bits;  integer: lo + floor(u (hi - lo));  continuous:
+ *   lo + u (hi - lo) in fp64, rounded to float32 on store;  every floor(u n) is capped at n - 1.
+ * Limits (refused before any launch): 1 <= nc m <= 2^22, 1 <= L <= 256, 1 <= d <= 2^20, 1 <= max_leaves <= L, weights
+ * non-negative and finite with a positive sum, 0 < alpha < 1, beta >= 0 and finite, 0 <= sweep < 2^32, offsets within 32 bits,
+ * record buffers on even addresses and distinct.  bounds (d, 2) fp64 in the reference's bitmask encoding (categorical:
+ * [0, mask]), feat_types (d) int64; both DEVICE.  One launch, no allocation, no synchronisation: capturable.
+ * bark_tree_proposals_commit_hip: nodes[c, tree_index[t]] <- new_nodes[c, tree_index[t]] wherever accept[t, c] > 0 (the
+ * (n_steps, nc) int32 tensor the sweeps write; tree_index DEVICE int64).
+ * ------------------------------------------------------------------------------------- */
+typedef struct {
+    double alpha, beta;
+    double weights[3];    /* grow, prune, change; normalised by their sum */
+    int64_t max_leaves;
+    int64_t chain_offset; /* added to the chain / tree index in the counter: a sub-batch draws what the whole batch draws */
+    int64_t tree_offset;
+} bark_proposal_params;
+typedef struct {
+    int64_t nodes_bytes;  /* of one (nc, m, L) record buffer; 0 when the shape is refused */
+    int32_t max_slots, max_features, max_proposals, threads, workgroups;
+} bark_tree_proposals_plan;
+int bark_tree_proposals_query(int64_t L, int64_t d, int64_t max_leaves, int64_t nc, int64_t m, bark_tree_proposals_plan *plan_out);
+int bark_tree_proposals_hip(bark_ctx *ctx, const void *nodes, int64_t nc, int64_t m, int64_t L, const double *bounds,
+                            const int64_t *feat_types, int64_t d, const bark_proposal_params *params, uint64_t seed, int64_t sweep,
+                            void *new_nodes, double *log_q_prior, double *log_u, int32_t *detail, void *stream);
+int bark_tree_proposals_commit_hip(void *nodes, const void *new_nodes, const int32_t *accept, const int64_t *tree_index,
+                                   int64_t n_steps, int64_t nc, int64_t m, int64_t L, void *stream);
+
 /* quick_inverse.py:37-38  mll(K_inv, K_logdet, y) = 0.5 * (-y' K_inv y - K_logdet), on device. */
 int bark_quadform_hip(const double *K_inv, const double *y, int64_t N, double *out, void *stream);
 /* out[b] = alpha * sum_i A[b * lda + i] * y[i] + beta * c[b] for b < B (c may be NULL) — e.g. log|K_s| =
