@@ -247,12 +247,6 @@ __global__ void init_rhs_kernel(const double *__restrict__ y, int N, int npad, d
     }
 }
 
-// a leaf walk of this call met an invalid categorical value: every sample of the chunk reports it (info = -1)
-__global__ void fault_info_kernel(const int32_t *fault, int32_t *info, int Bc) {
-    const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < Bc && *fault) info[b] = -1;
-}
-
 // quick_inverse.py:38 / mcmc_record_mll.py:73
 __global__ void finish_mll_kernel(const double *accum, int Bc, int N, int include_2pi, double *mll, const int32_t *fault,
                                   int32_t *info, const int32_t *sync) {
@@ -345,23 +339,6 @@ static int launch_predict_reduce(const Mats &p, int N, int C, int bc, const doub
         BARK_LAUNCH_CHECK();
     }
     return BARK_OK;
-}
-
-// y' K_inv y  (quick_inverse.py:38), one workgroup, grid-stride rows
-__global__ __launch_bounds__(THREADS) void quadform_kernel(const double *__restrict__ Kinv,
-                                                           const double *__restrict__ y, int N, double *out) {
-    __shared__ double red[THREADS / 64];
-    double total = 0.0;
-    for (int r = blockIdx.x; r < N; r += gridDim.x) {
-        double s = 0.0;
-        for (int c = threadIdx.x; c < N; c += THREADS) s = fma(Kinv[(size_t)r * N + c], y[c], s);
-        total = fma(s, y[r], total);
-    }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = total;
-    __syncthreads();
-    if (threadIdx.x == 0) atomicAdd(out, red[0] + red[1] + red[2] + red[3]);
 }
 
 }  // namespace

@@ -97,7 +97,35 @@ int launch_gram(const uint32_t *leaf1, int npad1, const uint32_t *leaf2, int npa
                 int Nout, int Mout, const double *shift, const double *scale, const double *noise, double *out, int64_t ld,
                 int64_t batch_stride, bool pad_identity, bool upper_only, int rep, int words, hipStream_t stream);
 
-// leafspace.hip: launchers of the leaf-space entry points (LeafSystem, chol.hip)
+// chol.hip: the lock-step Cholesky sweep for a unit that fills its own systems (leafsystem.hip) — Bc resident R x R matrices
+// A = U'U with one right-hand side each, and R identity columns appended when the caller also wants V = U^-T.  Host functions
+// over an opaque handle; the sweep's kernels, layout and schedules stay in chol.hip.
+struct SystemSweep;
+// The chunk's systems as the caller's kernels fill them before system_sweep_factor and read them after it.
+struct SystemMats {
+    double *A;           // (Bc, npad, ld), matrix stride bstride: the upper triangle of the systems on entry, U on exit
+    long ld, bstride;
+    double *yz;          // (Bc, npad): the right-hand sides v on entry, z = U^-T v on exit
+    double *accum;       // (Bc, 2): the sweep adds |z|^2 and log det A; the caller zeroes it, and its `info` (system_sweep_bind)
+    const double *V;     // the identity columns inside A (same ld and bstride): V = U^-T on exit
+    int64_t npad, cpad;  // R, and the identity columns (0 without), padded to whole blocks
+};
+// bytes at the front of the caller's workspace (256-byte aligned); needs no device
+size_t system_sweep_bytes(int64_t R, bool identity, int64_t m, int64_t Bc);
+// the sweep on `caller` and the context's helper streams; raises this unit's LDS limits first.  Closed by system_sweep_close.
+int system_sweep_open(bark_ctx *ctx, hipStream_t caller, void *workspace, int64_t R, bool identity, int64_t m, int64_t Bc,
+                      SystemSweep **out);
+void system_sweep_close(SystemSweep *s);
+// chunk(arg, c0, bc) for the chunks of at most Bc of the B systems, until one fails.  However a chunk returns, every helper
+// stream the sweep has put work on is joined back into the caller's stream before this returns.
+int system_sweep_chunks(SystemSweep *s, int64_t B, int64_t Bc, int (*chunk)(void *arg, int64_t c0, int64_t bc), void *arg);
+// first in a chunk: its size and where the sweep reports its pivot status (bc entries); -> what to fill
+const SystemMats &system_sweep_bind(SystemSweep *s, int64_t bc, int32_t *info);
+int system_sweep_factor(SystemSweep *s);             // the identity columns when opened with them, then the block steps
+int system_sweep_w(SystemSweep *s, double *w);       // after the factor, identity only: w = A^-1 v = V'z (bc, R)
+int system_sweep_minv(SystemSweep *s, double *Minv);  // ... and A^-1 = V'V (bc, R, R)
+
+// leafspace.hip: launchers of the leaf-space entry points (LeafSystem, leafsystem.hip)
 // leaf_inverse_kernel keeps the leaf lists of its 64 columns in dynamic LDS, m x 64 16-bit ids, so it takes forests of at
 // most 160 KiB / 128 B = 1280 trees
 constexpr int LEAF_INV_MAX_TREES = 1280;
@@ -150,7 +178,7 @@ int acq_scan(int variant, int kind, const uint32_t *ccodes, int W, int cpad, int
 int acq_finish(const double *acc, int64_t C, int B, double kappa, int kind, const int64_t *skip, int n_skip, double *acq_out,
                double *part_v, int64_t *part_i, const int32_t *info, double *best, int64_t *best_i, hipStream_t s);
 
-// scores.hip (entry points; their host driver is LeafSystem's, chol.hip)
+// scores.hip (launchers of bark_predictive_scores_hip, leafsystem.hip)
 // n points of one slab, whose first tile is tile0 of the call's `tiles`, against the bc forests of the chunk: the mixture's
 // running state per point in the slab's part of acc (3, C; row stride astride) and one partial pair per (forest, tile) in
 // fpart (bc, tiles, 2).  variant as acq_scan; mode: BARK_SCORE_*; info: the chunk's sweep status; yp: the slab's targets
@@ -162,13 +190,6 @@ int score_forests(const double *fpart, int tiles, int bc, double *rows, hipStrea
 // the per-point mixture terms (values_out (2, C) or null), their sums through mpart (tiles, 2), and NaN wherever info says so
 int score_finish(const double *acc, int64_t C, int B, const double *yp, double *values_out, double *mpart, const int32_t *info,
                  double *per_forest_out, double *mixture_out, hipStream_t s);
-// chol.hip: what bark_predictive_scores_workspace_bytes / bark_predictive_scores_hip do once the arguments of their own are
-// checked (variant resolved by bark_acquisition_plan)
-size_t scores_workspace_bytes(int64_t N, int64_t R, int64_t m, int64_t Bc, int64_t C);
-int scores_run(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d, const double *y,
-               const double *noise, const double *scale, const double *points, int64_t C, const double *y_points, int mode,
-               int variant, double *per_forest_out, double *mixture_out, double *values_out, int32_t *info_out, void *workspace,
-               size_t workspace_bytes, int64_t Bc, void *stream);
 
 constexpr size_t STAGE_BYTES = 64 * 1024;  // bark_ctx::stage_host / stage_dev
 constexpr int NODE_BYTES = 26;          // forest.py:8-19, packed
@@ -180,6 +201,7 @@ constexpr int TILE = 128;  // Cholesky block size == MFMA tile edge per workgrou
 constexpr int MAX_LEAF_WORDS = 112;  // leaf-code dwords per point the Gram kernels can stage in LDS
 
 inline int64_t round_up(int64_t x, int64_t q) { return (x + q - 1) / q * q; }
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }  // workspace areas start on 256-byte boundaries
 
 // Number of differing bytes of two dwords that each pack 4 dense leaf ids (one tree per byte): a tree pair
 // agrees iff its byte of a ^ b is zero.  Ids < 128 keep bit 7 clear, so `x + 0x7f7f7f7f` cannot carry

@@ -7,7 +7,8 @@
 //     y' K_s^-1 y   = ( y'y - c v' (I_R + c Z'Z)^-1 v ) / sigma2 ,  v = Z'y     (Woodbury)
 // so the O(N^3) factorisation of the reference (mcmc_record_mll.py:69-70, bark_sampler.py:157-159) becomes an
 // R x R one (R ~ 150 for 50 prior trees).  Z'Z[a][b] is a co-occurrence count = popcount over points of
-// (bit-plane a AND bit-plane b); the R x R system is then handed to the same blocked Cholesky sweep (chol.hip).
+// (bit-plane a AND bit-plane b); the R x R system is then handed to the same blocked Cholesky sweep (chol.hip, through
+// SystemSweep) by the entry points' host driver (leafsystem.hip).
 // This path does NOT perform the Gram + N x N Cholesky work the benchmark metric counts and is never used
 // by bench.py's timed region; it exists because it is the cheaper exact algorithm for the same quantity.
 #include "common.h"
@@ -337,7 +338,7 @@ int leafspace_inverse(const uint32_t *codes, int W, int npad, int N, const doubl
     return BARK_OK;
 }
 
-// launchers used by the entry point in chol.hip -----------------------------------------------------------
+// launchers used by LeafSystem (leafsystem.hip) -----------------------------------------------------------
 int leafspace_prepare(const uint32_t *codes, int W, int npad, unsigned long long *planes, int R, int Rpad,
                       const double *noise, const double *scale, int m, int bc, double *A, long ld, long bstride,
                       const double *y, int N, double *yz, double *accum, int32_t *info, hipStream_t s) {

@@ -2,7 +2,7 @@
 //
 // With Z the one-hot leaf matrix, M = I_R + c Z'Z = U'U, w = M^-1 Z'y, c = scale / (m s2), the leaf weights of the
 // forest's latent function f(x) = sum_t W[leaf_t(x)] have the posterior  W ~ N(c w, (scale/m) M^-1).  The leaf-space
-// sweep with the identity right-hand side (chol.hip, LeafSystem) leaves V = U^-T in the extra block columns, and
+// sweep with the identity right-hand side (LeafSystem, leafsystem.hip) leaves V = U^-T in the extra block columns, and
 // U^-1 U^-T = M^-1, so one draw is  W_s = c w + sqrt(scale/m) V' eps_s.  Two kernels per chunk of forests:
 //   sample_weights_kernel   Wt[a][s] = c w[a] + sqrt(scale/m) sum_k V[k][a] eps[s][k]   (fp64 MFMA; leaf-major, so a row
 //                           of Wt holds every draw of one leaf)

@@ -217,29 +217,3 @@ int score_finish(const double *acc, int64_t C, int B, const double *yp, double *
 }
 
 }  // namespace bark
-
-using namespace bark;
-
-extern "C" size_t bark_predictive_scores_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t Bc, int64_t C) {
-    if (N < 1 || max_bits < 1 || m < 1 || Bc < 1 || C < 1) return 0;
-    return scores_workspace_bytes(N, max_bits, m, Bc, C);
-}
-
-extern "C" int bark_predictive_scores_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N,
-                                          int64_t d, const double *y, const double *noise, const double *scale,
-                                          const double *points, int64_t C, const double *y_points, int mode, int variant,
-                                          double *per_forest_out, double *mixture_out, double *values_out, int32_t *info_out,
-                                          void *workspace, size_t workspace_bytes, int64_t Bc, void *stream) {
-    error_buffer()[0] = 0;
-    if (!info || !scale || !points || !y_points || !per_forest_out || !mixture_out)
-        return fail(BARK_ERR_ARG, "bark_predictive_scores_hip: null argument");
-    if (C < 1) return fail(BARK_ERR_ARG, "bark_predictive_scores_hip: bad shape C=%lld", (long long)C);
-    if (mode != BARK_SCORE_HELDOUT && mode != BARK_SCORE_LOO) return fail(BARK_ERR_ARG, "bark_predictive_scores_hip: unknown mode %d", mode);
-    if (mode == BARK_SCORE_LOO && C != N)
-        return fail(BARK_ERR_ARG, "bark_predictive_scores_hip: leave-one-out scores are taken at the N = %lld training points (got C = %lld)",
-                    (long long)N, (long long)C);
-    int var = 0, rc;
-    if ((rc = bark_acquisition_plan(info->max_bits, info->m, variant, &var, nullptr))) return rc;
-    return scores_run(ctx, packed, info, X, N, d, y, noise, scale, points, C, y_points, mode, var, per_forest_out, mixture_out, values_out,
-                      info_out, workspace, workspace_bytes, Bc, stream);
-}

@@ -481,6 +481,54 @@ def test_error_return_rejoins_helper_streams(env):
             assert bool((wl.mll_d == good).all()) and int(wl.info_d.abs().max().item()) == 0, (what, k)
 
 
+def test_leafspace_error_return_rejoins_helper_streams(env):
+    """The same invariant for the leaf-space side, whose chunk loop reaches the sweep across a unit boundary:
+    bark_mll_leafspace_hip with candidates (identity columns, w and M^-1, predict) on forests of R = 130 leaves — two block
+    rows, so block step 1 puts its row launch on a helper stream (Sweep::step: rows_off_stream) — B = 3 forests in chunks of 2.
+    A call makes 1 + 16 per chunk checked launches (y'y | walk, 3 x prepare, identity, diag 0, solve 0, diag 1, rows 1 on
+    the helper stream, solve 1, MLL, w, M^-1, candidate walk, predict, close); the failure is injected at the third (before
+    the sweep's first launch), at the row launch of the first chunk and at the row launch of the second.  The call raises,
+    the countdown was consumed, and after a synchronize the next call on the same context and workspace returns mll, mu
+    and var bit for bit as before, with info all zero."""
+    import leafspace_ref as lr
+    from bark_amd.fitting.mll import _leaf_inputs
+
+    torch, L, lib = env.torch, env.lib, env.lib.lib()
+    inp = lr.make_inputs(lr.Case("fault", ((("full", 8, 4), ("null", 2)),), N=200, B=3, shape=(), C=50, S=1, chunk=2, seed=21))
+    q = _leaf_inputs(inp.F, inp.noise, inp.scale, inp.X, inp.y, inp.ft, inp.cand)
+    B, C, Bc = q.B, q.C, 2
+    assert (q.R, q.m, B, C) == (130, 10, 3, 50)
+    ws = L.workspace(int(lib.bark_mll_leafspace_workspace_bytes(q.N, q.R, q.m, Bc, C)))
+    mll, mu, var = (torch.empty(s, dtype=torch.float64, device=q.device) for s in ((B,), (B, C), (B, C)))
+    info = torch.empty(B, dtype=torch.int32, device=q.device)
+
+    def run():
+        for t in (mll, mu, var):
+            t.fill_(float("nan"))
+        info.fill_(-7)
+        L.check(lib.bark_mll_leafspace_hip(L.ctx(), L.ptr(q.pf.packed), q.pf.info_ref, L.ptr(q.Xd), q.N, q.d, L.ptr(q.yd),
+                                           L.ptr(q.noise_d), L.ptr(q.scale_d), L.MLL_INCLUDE_SCALE, L.ptr(q.cand_d), C, L.ptr(mll),
+                                           L.ptr(mu), L.ptr(var), L.ptr(info), L.ptr(ws), ws.numel(), Bc, L.stream_ptr()))
+
+    armed = 1000
+    assert lib.bark_debug_fail_launch(armed) == 0
+    run()
+    per_chunk = 16
+    assert armed - lib.bark_debug_fail_launch(0) == 1 + 2 * per_chunk  # the sequence the three k below are counted in
+    torch.cuda.synchronize()
+    good = [t.clone() for t in (mll, mu, var)]
+    assert all(bool(torch.isfinite(t).all()) for t in good) and int(info.abs().max().item()) == 0
+    for k in (3, 1 + 9, 1 + per_chunk + 9):
+        assert lib.bark_debug_fail_launch(k) == 0
+        with pytest.raises(RuntimeError, match="hipErrorLaunchFailure|unspecified launch failure|failed"):
+            run()
+        assert lib.bark_debug_fail_launch(0) == 0, k  # the countdown was consumed by this call
+        torch.cuda.synchronize()  # nothing of the failed call is left running or waiting
+        run()
+        torch.cuda.synchronize()
+        assert all(bool((t == g).all()) for t, g in zip((mll, mu, var), good)) and int(info.abs().max().item()) == 0, k
+
+
 _CAPTURE_FAULT_SCRIPT = r"""
 import sys
 sys.path.insert(0, {root!r})
