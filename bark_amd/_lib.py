@@ -25,6 +25,7 @@ MLL_INCLUDE_SCALE, MLL_INCLUDE_2PI, MLL_RHS_IDENTITY = 1, 2, 4
 SAMPLE_FULL, SAMPLE_MAX, SAMPLE_MIN = 0, 1, 2  # BARK_SAMPLE_*
 ACQ_LCB_MEAN, ACQ_LCB_MIXTURE, ACQ_EI, ACQ_PI, ACQ_MES = 0, 1, 2, 3, 4  # BARK_ACQ_*
 SCORE_HELDOUT, SCORE_LOO = 0, 1  # BARK_SCORE_*
+DOMAIN_UNIFORM, DOMAIN_CELLS, DOMAIN_GRID = 0, 1, 2  # BARK_DOMAIN_*
 
 i64, vp, ci = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
 
@@ -118,6 +119,8 @@ SIGNATURES = {
     "bark_tree_proposals_query": (ci, [i64, i64, i64, i64, i64, vp]),
     "bark_tree_proposals_hip": (ci, [vp, vp, i64, i64, i64, vp, vp, i64, vp, ctypes.c_uint64, i64, vp, vp, vp, vp, vp]),
     "bark_tree_proposals_commit_hip": (ci, [vp, vp, vp, vp, i64, i64, i64, i64, vp]),
+    "bark_domain_candidates_hip": (ci, [vp, vp, i64, vp, vp, i64, ci, ctypes.c_uint64, i64, i64, i64, vp, vp]),
+    "bark_domain_neighbours_hip": (ci, [vp, vp, i64, i64, vp, i64, vp, vp]),
     "bark_noise_scale_step_chains_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64]),
     "bark_noise_scale_step_chains_hip": (ci, [vp, vp, i64, i64, vp, ctypes.POINTER(PackInfo), vp, i64, vp, vp, vp, vp, vp, vp,
                                               vp, vp, ctypes.c_size_t, vp]),

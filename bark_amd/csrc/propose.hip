@@ -18,6 +18,7 @@
 //   block 0: draw 0 kind, draw 1 node;  block 1: draw 2 feature, draw 3 threshold or mask;  block 2: draw 4 accept.
 // A proposal's bits depend on (seed, sweep, chain, tree) only.
 #include "common.h"
+#include "philox.h"
 
 #include <cmath>
 
@@ -62,24 +63,7 @@ __device__ __forceinline__ uint32_t rd32(const unsigned char *tree, uint32_t slo
 }
 constexpr int O_LEAF = 0, O_FEAT = 1, O_THR = 5, O_LEFT = 9, O_RIGHT = 13, O_PARENT = 17, O_DEPTH = 21, O_ACTIVE = 25;
 
-__device__ __forceinline__ void philox(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
-        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
-        c1 = (uint32_t)p1, c3 = (uint32_t)p0, c0 = n0, c2 = n2;
-        k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-    }
-    out[0] = c0, out[1] = c1, out[2] = c2, out[3] = c3;
-}
-__device__ __forceinline__ double uniform53(uint32_t lo, uint32_t hi) {
-    return (double)((((uint64_t)hi << 32) | lo) >> 11) * 0x1p-53;
-}
-// floor(u n) in 0 .. n - 1 (u n can round up to n)
-__device__ __forceinline__ int64_t pick(double u, int64_t n) {
-    const int64_t k = (int64_t)(u * (double)n);
-    return k < n ? k : n - 1;
-}
+// philox, uniform53 and pick: philox.h
 // k-th set bit (k < popcount) of a wave-uniform mask
 __device__ __forceinline__ int kth_bit(uint64_t mask, int k) {
     for (int j = 0; j < k; ++j) mask &= mask - 1;

@@ -1,4 +1,4 @@
-"""Philox4x32-10 in numpy integers: the host half of the sampler's random stream (csrc/propose.hip holds the device half).
+"""Philox4x32-10 in numpy integers: the host half of the sampler's random stream (csrc/philox.h holds the device half).
 Private.  key = (seed low word, seed high word), counter = (chain, tree, sweep, block); words (0, 1) and (2, 3) of a block are
 one 64-bit draw each, low word first, and a uniform double is (x >> 11) * 2^-53."""
 

@@ -1,6 +1,8 @@
 """Drop-in for the sampling helpers of `bark.optimizer` (reference: src/bark/optimizer/), built on the leaf-space
-posterior draws of `bark_amd.tree_kernels.posterior_samples`, and the acquisition scan over a candidate set that stands
-in for the reference's solver-based `propose` (`acquisition`)."""
+posterior draws of `bark_amd.tree_kernels.posterior_samples`, the acquisition scan over a candidate set (`acquisition`) and
+the search over the whole domain that stands in for the reference's solver-based `propose` (`domain`)."""
 
 from .acquisition import (acquisition_plan, acquisition_scan, propose_batch_from_candidates,  # noqa: F401
                           propose_from_candidates, propose_mes_from_candidates)
+from .domain import (CellTable, domain_candidates, domain_neighbours, domain_plan, propose_from_domain,  # noqa: F401
+                     split_table)

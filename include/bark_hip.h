@@ -741,6 +741,39 @@ int bark_tree_proposals_hip(bark_ctx *ctx, const void *nodes, int64_t nc, int64_
 int bark_tree_proposals_commit_hip(void *nodes, const void *new_nodes, const int32_t *accept, const int64_t *tree_index,
                                    int64_t n_steps, int64_t nc, int64_t m, int64_t L, void *stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Domain candidates — the search space of the reference's `propose` (optimizer/opt_core.py, proposals.py) as rows for the
+ * acquisition scan.  The posterior of a tree kernel is piecewise constant: the thresholds of all trees of all forest samples
+ * cut the range of every feature into cells, the acquisition takes one value on each product cell, and one representative
+ * per cell stands for all of its points.  The cell table (built on the host, bark_amd/optimizer/domain.py; DEVICE memory here):
+ *   cell_off (d + 1) int64: feature f owns the slots cell_off[f] .. cell_off[f + 1] - 1;  cell_rep (total) fp64.
+ * bark_domain_candidates_hip writes rows first .. first + n - 1 of a conceptual candidate list into out (n, d) fp64, row-major:
+ *   mode = BARK_DOMAIN_UNIFORM  continuous: lo + u (hi - lo), capped at hi;  integer: lo + floor(u (hi - lo + 1));  categorical:
+ *                               the floor(u k)-th of the k set bits of the mask.  Reads bounds (d, 2) fp64 in the reference's
+ *                               bitmask encoding and feat_types (d) int64, both DEVICE; the table may be NULL.
+ *   mode = BARK_DOMAIN_CELLS    feature f takes cell_rep[cell_off[f] + floor(u cells_f)]: uniform over cells, not over volume.
+ *   mode = BARK_DOMAIN_GRID     no draws: row i is the i-th element of the Cartesian product of the cells, feature d - 1 varying
+ *                               fastest (itertools.product), decoded as mixed radix in 64-bit arithmetic.  The caller keeps
+ *                               first + n within the grid.
+ *   Draws: Philox4x32-10 as the tree proposals use it, key = (seed low word, seed high word ^ 0x646F6D61), counter = (i low
+ *   word, i high word, round, block) with i the GLOBAL row index; feature f uses draw f of its row: block f / 2, word pair
+ *   f % 2; every floor(u n) is capped at n - 1.  A row depends on (seed, round, i) only — not on first, n or the launch.
+ *   bounds and feat_types are read in mode uniform only and may be NULL otherwise.
+ * bark_domain_neighbours_hip: x (K, d) -> out (K total, d); row (k, j) is x[k] with the feature that owns slot j replaced by
+ *   cell_rep[j] (moves inside the point's own cell are kept: the layout is fixed).
+ * Limits (refused before any launch): 1 <= d <= 4096, d <= total <= 2^20, 0 <= n <= 2^32, first >= 0, 0 <= round < 2^32,
+ * K total <= 2^24 (the scan's candidate limit), a null table where the mode reads it.  n == 0 / K == 0: nothing is launched.
+ * One launch each, no allocation, no synchronisation: capturable.
+ * ------------------------------------------------------------------------------------- */
+#define BARK_DOMAIN_UNIFORM 0
+#define BARK_DOMAIN_CELLS 1
+#define BARK_DOMAIN_GRID 2
+int bark_domain_candidates_hip(const int64_t *cell_off, const double *cell_rep, int64_t total, const double *bounds,
+                               const int64_t *feat_types, int64_t d, int mode, uint64_t seed, int64_t round, int64_t first, int64_t n,
+                               double *out, void *stream);
+int bark_domain_neighbours_hip(const int64_t *cell_off, const double *cell_rep, int64_t total, int64_t d, const double *x, int64_t K,
+                               double *out, void *stream);
+
 /* quick_inverse.py:37-38  mll(K_inv, K_logdet, y) = 0.5 * (-y' K_inv y - K_logdet), on device. */
 int bark_quadform_hip(const double *K_inv, const double *y, int64_t N, double *out, void *stream);
 /* out[b] = alpha * sum_i A[b * lda + i] * y[i] + beta * c[b] for b < B (c may be NULL) — e.g. log|K_s| =

@@ -1,0 +1,78 @@
+"""What optimizer.propose_from_domain reaches, and how long it takes, beside what a user did before it existed: torch.rand
+candidates in the box, as many as the search scores, through acquisition_scan ("Search over the domain").
+
+  exhaustive   a small problem whose cell grid is enumerated: the exact minimiser
+  search       B = 64, m = 50, N = 512, d = 10: multi-start local search from `cells` candidates
+  random       the same problem, C uniform candidates in the box in one scan, C = the rows the search scored
+
+The value reached is the result; wall time (host clock around the call, which ends in a read-back) is context.  Median of 5
+after 2 warm-ups.  Usage: PYTHONPATH=$PWD python tools/time_domain_search.py"""
+import json
+import time
+
+import numpy as np
+
+WARMUP, REPS = 2, 5
+
+
+def measure(fn):
+    import torch
+
+    for _ in range(WARMUP):
+        out = fn()
+    times = []
+    for _ in range(REPS):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e3)
+    return float(np.median(times)), out
+
+
+def main():
+    import torch
+
+    import bark_amd.synthetic as syn
+    from bark_amd.optimizer import acquisition_scan, domain_plan, propose_from_domain, split_table
+
+    # exhaustive: d = 4 mixed, 8 forests of 10 trees
+    X, y, bounds, ft = syn.mixed_problem(64, seed=1, d_cont=2, n_int=1, n_cat=1, cats=5)
+    F = syn.sample_prior_forests(8, 10, bounds, ft, seed=3)
+    model = (F, np.linspace(0.05, 0.3, 8), np.linspace(0.7, 1.4, 8))
+    plan = domain_plan(split_table(F, bounds, ft))
+    ms, (x, info) = measure(lambda: propose_from_domain(model, (X, y), bounds, ft, return_info=True))
+    print(json.dumps({"route": "exhaustive", "B": 8, "m": 10, "N": 64, "d": 4, "grid": plan["grid"], "value": info["value"],
+                      "scans": info["scans"], "ms": round(ms, 2)}), flush=True)
+
+    # search: B = 64, m = 50, N = 512, d = 10
+    B, m, N = 64, 50, 512
+    X, y, bounds, ft = syn.mixed_problem(N, seed=1, d_cont=6)
+    F = syn.sample_prior_forests(B, m, bounds, ft, seed=3)
+    model = (F, np.linspace(0.05, 0.3, B), np.linspace(0.7, 1.4, B))
+    data = (torch.as_tensor(X, device="cuda"), torch.as_tensor(y, device="cuda"))
+    plan = domain_plan(split_table(F, bounds, ft))
+    ms, (x, info) = measure(lambda: propose_from_domain(model, data, bounds, ft, seed=5, return_info=True))
+    scored = 2 ** 18 + info["sweeps"] * 8 * plan["neighbours"]
+    print(json.dumps({"route": "search", "B": B, "m": m, "N": N, "d": 10, "grid": float(plan["grid"]), "cells": plan["neighbours"],
+                      "value": info["value"], "best_start": float(info["start_values"][0]), "sweeps": info["sweeps"],
+                      "scans": info["scans"], "rows_scored": scored, "ms": round(ms, 2)}), flush=True)
+
+    lo = torch.as_tensor(bounds[:, 0], device="cuda")
+    hi = torch.as_tensor(np.where(ft == syn.CAT, 5.0, bounds[:, 1] + (ft == syn.INT)), device="cuda")  # integers, categories: floor
+    discrete = torch.as_tensor(ft != syn.CONT, device="cuda")
+
+    def random_route(C):
+        gen = torch.Generator(device="cuda").manual_seed(5)
+        cand = lo + torch.rand((C, 10), dtype=torch.float64, device="cuda", generator=gen) * (hi - lo)
+        cand = torch.where(discrete, cand.floor(), cand)
+        value, _ = acquisition_scan(model, data, cand, ft)
+        return float(value)
+
+    for C in (2 ** 18, min(scored, 2 ** 24)):
+        ms, value = measure(lambda: random_route(C))
+        print(json.dumps({"route": "random", "C": C, "value": value, "ms": round(ms, 2)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
