@@ -73,6 +73,7 @@ SIGNATURES = {
     "bark_mll_plan_query": (ci, [i64, i64, i64, i64, i64, ci, ci, ctypes.POINTER(MllPlan)]),
     "bark_debug_fail_launch": (ctypes.c_long, [ctypes.c_long]),
     "bark_frontend_variant_query": (ci, [ctypes.POINTER(PackInfo), i64, i64, i64, i64, i64, ci, ctypes.POINTER(FrontendVariant)]),
+    "bark_debug_metropolis": (ci, [ctypes.c_double, ctypes.c_double, ctypes.c_double]),
     "bark_dev_alloc": (ci, [vp, ctypes.c_size_t, ctypes.POINTER(vp)]),
     "bark_dev_free": (ci, [vp, vp]),
     "bark_ctx_upload": (ci, [vp, vp, vp, ctypes.c_size_t, vp]),

@@ -17,7 +17,7 @@
 // Conditioning: cond(M) ~ N scale / s2; like every leaf-space path this one loses digits as noise -> 0, so it is opt-in.
 #include <algorithm>
 
-#include "common.h"
+#include "sampler_step.h"  // -> common.h
 
 namespace bark {
 namespace {
@@ -25,9 +25,8 @@ namespace {
 constexpr int LC_THREADS = 512, LC_WAVES = LC_THREADS / 64;
 constexpr int LC_LCAP = 32;     // leaves per tree; also the row pitch of the Rcap x r scratch matrices
 constexpr int LC_RCAP = 1024;   // slots per chain
-constexpr int LC_TREES = 64, LC_CHAINS = 64;
+constexpr int LC_TREES = 64;
 constexpr int LC_STRIDE_MAX = 64;  // packed nodes per tree walked from LDS (a tree of 32 leaves has 63)
-constexpr int LC_TABLE_WORDS = 4;  // per step: offset, stride, max_depth, tree index
 constexpr int LC_SP = LC_LCAP + 1; // pitch of the small matrices in LDS
 typedef unsigned long long u64;
 
@@ -64,7 +63,8 @@ LcLayout lc_layout(int64_t N, int64_t Rcap, int64_t m, int64_t lcap) {
 }
 
 int lc_check_shape(int64_t N, int64_t Rcap, int64_t m, int64_t lcap, int64_t nc, int64_t d) {
-    if (nc < 1 || nc > LC_CHAINS) return fail(BARK_ERR_ARG, "leaf-space chains: %lld chains are outside 1..%d", (long long)nc, LC_CHAINS);
+    if (nc < 1 || nc > SAMPLER_MAX_CHAINS)
+        return fail(BARK_ERR_ARG, "leaf-space chains: %lld chains are outside 1..%d", (long long)nc, SAMPLER_MAX_CHAINS);
     if (m < 1 || m > LC_TREES) return fail(BARK_ERR_ARG, "leaf-space chains: %lld trees are outside 1..%d", (long long)m, LC_TREES);
     if (lcap < 1 || lcap > LC_LCAP)
         return fail(BARK_ERR_ARG, "leaf-space chains: %lld leaves per tree are outside 1..%d", (long long)lcap, LC_LCAP);
@@ -109,11 +109,6 @@ __device__ __forceinline__ LcChain lc_chain(const LcArgs &p, int b) {
     return c;
 }
 
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 __device__ __forceinline__ double wave_sum(double s) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
@@ -354,8 +349,7 @@ __global__ __launch_bounds__(LC_THREADS) void leafchain_noise_scale_kernel(LcArg
         } else {
             lc_state(scal[0], scal[1], c.hdr[H_YY], noise, scale, m, N, &quad, &logdet);
             const double new_mll = 0.5 * (-quad - logdet), cur_mll = 0.5 * (-p.mstate[2 * b] - p.mstate[2 * b + 1]);
-            const double log_alpha = p.log_q_prior[b] + (new_mll - cur_mll);
-            acc = (p.log_u[b] <= log_alpha && p.log_u[b] <= 0.0) ? 1 : 0;
+            acc = metropolis_accept(p.log_u[b], p.log_q_prior[b], new_mll - cur_mll);
         }
         p.accept_out[b] = acc;
         if (acc > 0) {
@@ -432,12 +426,10 @@ __global__ __launch_bounds__(LC_THREADS) void leafchain_sweep_kernel(LcArgs p) {
             if (tid == 0) p.accept_out[(size_t)t * nc + b] = -1;
             continue;
         }
-        const int64_t *hd = p.table + (size_t)t * LC_TABLE_WORDS;
-        const int stride = min(max((int)hd[1], 1), LC_STRIDE_MAX), max_depth = (int)hd[2];  // the table builder checked
-        const int tree = min(max((int)hd[3], 0), m - 1);
-        const int r_new = min(max((int)p.table[(size_t)p.n_steps * LC_TABLE_WORDS + (size_t)t * nc + b], 1), lcap);
+        const StepEntry st = step_entry(p.table, t, p.n_steps, nc, b, LC_STRIDE_MAX);
+        const int stride = st.stride, max_depth = st.max_depth, tree = min(max(st.word3, 0), m - 1), r_new = min(max(st.column, 1), lcap);
         const int r_old = min(max(c.nleaves[tree], 1), lcap);
-        const uint4 *nodes = reinterpret_cast<const uint4 *>(p.packed + hd[0]) + (size_t)b * stride;
+        const uint4 *nodes = reinterpret_cast<const uint4 *>(p.packed + st.offset) + (size_t)b * stride;
         __syncthreads();  // the slot map, inT / newidx and the state of the previous step
         if (r_new - r_old > *c.nfree) {  // cannot happen after the host's capacity check; never overflow the stack
             latched = true;
@@ -628,9 +620,7 @@ __global__ __launch_bounds__(LC_THREADS) void leafchain_sweep_kernel(LcArgs p) {
                     nq = sc[1] + part;
                     nlogm = logm + sc[0] + ldS;
                     lc_state(nq, nlogm, yy, noise, scale, m, N, &nquad, &nlogdet);
-                    const double log_alpha = p.log_q_prior[at] + (0.5 * (-nquad - nlogdet) - 0.5 * (-quad - logdet));
-                    const double lu = p.log_u[at];
-                    acc = (lu <= log_alpha && lu <= 0.0) ? 1 : 0;  // a NaN on either side compares false: reject
+                    acc = metropolis_accept(p.log_u[at], p.log_q_prior[at], 0.5 * (-nquad - nlogdet) - 0.5 * (-quad - logdet));
                 }
                 p.accept_out[at] = acc;
                 if (acc > 0) {
@@ -737,7 +727,7 @@ int bark_leafchain_query(int64_t N, int64_t Rcap, int64_t m, int64_t lcap, int64
     error_buffer()[0] = 0;
     if (!out) return fail(BARK_ERR_ARG, "bark_leafchain_query: null argument");
     *out = bark_leafchain_plan{};
-    out->max_chains = LC_CHAINS, out->max_trees = LC_TREES, out->max_leaves = LC_LCAP, out->max_slots = LC_RCAP;
+    out->max_chains = SAMPLER_MAX_CHAINS, out->max_trees = LC_TREES, out->max_leaves = LC_LCAP, out->max_slots = LC_RCAP;
     out->max_nodes = LC_STRIDE_MAX;
     const int rc = lc_check_shape(N, Rcap, m, lcap, nc, d);
     if (rc) return rc;
@@ -789,8 +779,8 @@ int bark_leafchain_init_hip(bark_ctx *ctx, void *state, int64_t N, int64_t Rcap,
 }
 
 size_t bark_leafchain_sweep_table_bytes(int64_t n_steps, int64_t nc) {
-    if (n_steps < 1 || nc < 1 || nc > LC_CHAINS || n_steps > ((int64_t)1 << 30)) return 0;
-    return (size_t)(n_steps * (LC_TABLE_WORDS + nc)) * sizeof(int64_t);
+    if (n_steps < 1 || nc < 1 || nc > SAMPLER_MAX_CHAINS || n_steps > ((int64_t)1 << 30)) return 0;
+    return (size_t)(n_steps * (STEP_TABLE_WORDS + nc)) * sizeof(int64_t);
 }
 
 int bark_leafchain_sweep_table(const int64_t *packed_offsets, const bark_pack_info *infos, const int64_t *tree_index,
@@ -802,15 +792,10 @@ int bark_leafchain_sweep_table(const int64_t *packed_offsets, const bark_pack_in
         return fail(BARK_ERR_ARG, "bark_leafchain_sweep_table: bad argument");
     const int rc = lc_check_shape(1, Rcap, m, lcap, nc, 1);
     if (rc) return rc;
+    const StepPackRule rule{"leaf-space chains", "one new tree", "", 1, LC_STRIDE_MAX, false};
     for (int64_t t = 0; t < n_steps; ++t) {
         const bark_pack_info &in = infos[t];
-        if (in.B != nc || in.m != 1)
-            return fail(BARK_ERR_ARG, "step %lld: pack one new tree per chain (B = chains, m = 1)", (long long)t);
-        if (in.stride < 1 || in.stride > LC_STRIDE_MAX)
-            return fail(BARK_ERR_ARG, "leaf-space chains, step %lld: %lld packed nodes in a tree, at most %d", (long long)t,
-                        (long long)in.stride, LC_STRIDE_MAX);
-        if (packed_offsets[t] < 0 || packed_offsets[t] % 16 != 0 || in.max_depth < 0 || in.max_depth > (1 << 24))
-            return fail(BARK_ERR_ARG, "step %lld: bad offset or depth", (long long)t);
+        if (step_pack_check(rule, t, packed_offsets[t], in, nc)) return BARK_ERR_ARG;
         if (tree_index[t] < 0 || tree_index[t] >= m)
             return fail(BARK_ERR_ARG, "step %lld: tree index %lld is outside 0..%lld", (long long)t, (long long)tree_index[t], (long long)m - 1);
         for (int64_t b = 0; b < nc; ++b)
@@ -832,14 +817,7 @@ int bark_leafchain_sweep_table(const int64_t *packed_offsets, const bark_pack_in
             return fail(BARK_ERR_ARG, "leaf-space chains, chain %lld: the sweep may need %lld slots, the capacity is %lld; rebuild the "
                         "chains with a larger capacity", (long long)b, (long long)need, (long long)Rcap);
     }
-    int64_t *out = static_cast<int64_t *>(table_host_out);
-    for (int64_t t = 0; t < n_steps; ++t) {
-        out[t * LC_TABLE_WORDS + 0] = packed_offsets[t];
-        out[t * LC_TABLE_WORDS + 1] = infos[t].stride;
-        out[t * LC_TABLE_WORDS + 2] = infos[t].max_depth;
-        out[t * LC_TABLE_WORDS + 3] = tree_index[t];
-    }
-    for (int64_t e = 0; e < n_steps * nc; ++e) out[n_steps * LC_TABLE_WORDS + e] = r_new[e];
+    step_table_write(static_cast<int64_t *>(table_host_out), packed_offsets, infos, tree_index, r_new, n_steps, nc);
     return BARK_OK;
 }
 

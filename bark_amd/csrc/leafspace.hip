@@ -11,7 +11,7 @@
 // SystemSweep) by the entry points' host driver (leafsystem.hip).
 // This path does NOT perform the Gram + N x N Cholesky work the benchmark metric counts and is never used
 // by bench.py's timed region; it exists because it is the cheaper exact algorithm for the same quantity.
-#include "common.h"
+#include "sampler_step.h"  // -> common.h
 
 namespace bark {
 namespace {
@@ -282,8 +282,7 @@ __global__ void noise_scale_decide_kernel(const double *__restrict__ new_mll, co
         acc = -1;
     } else {
         const double cur_mll = 0.5 * (-state[2 * b] - state[2 * b + 1]);
-        const double log_alpha = log_q_prior[b] + (new_mll[b] - cur_mll);
-        acc = (log_u[b] <= log_alpha && log_u[b] <= 0.0) ? 1 : 0;
+        acc = metropolis_accept(log_u[b], log_q_prior[b], new_mll[b] - cur_mll);
     }
     accept_out[b] = acc;
 }

@@ -7,7 +7,7 @@
 // kernels in leafspace.hip, sample.hip, acquire.hip and scores.hip; this unit's only kernel is fault_info_kernel.
 #include <cmath>
 
-#include "common.h"
+#include "sampler_step.h"  // -> common.h
 
 namespace bark {
 namespace {
@@ -515,7 +515,8 @@ int bark_noise_scale_step_chains_hip(bark_ctx *ctx, double *K_inv, int64_t N, in
     error_buffer()[0] = 0;
     if (!K_inv || !info || !new_scale || !log_q_prior || !log_u || !state)
         return fail(BARK_ERR_ARG, "bark_noise_scale_step_chains_hip: null argument");
-    if (nc < 1 || nc > 64) return fail(BARK_ERR_ARG, "bark_noise_scale_step_chains_hip: 1 to 64 chains (got %lld)", (long long)nc);
+    if (nc < 1 || nc > SAMPLER_MAX_CHAINS)
+        return fail(BARK_ERR_ARG, "bark_noise_scale_step_chains_hip: 1 to %d chains (got %lld)", SAMPLER_MAX_CHAINS, (long long)nc);
     if (info->B != nc)
         return fail(BARK_ERR_ARG, "bark_noise_scale_step_chains_hip: %lld packed forests for %lld chains", (long long)info->B,
                     (long long)nc);

@@ -15,7 +15,7 @@
 // the right factor is U' K_inv, computed as its own pass when `symmetric == 0`.
 #include <vector>
 
-#include "common.h"
+#include "sampler_step.h"  // -> common.h
 
 namespace bark {
 namespace {
@@ -34,15 +34,14 @@ typedef double lr_double2 __attribute__((ext_vector_type(2)));
 // Several independent chains in one launch: the chain index is the highest grid dimension a kernel does not use
 // otherwise; chain b's matrices sit `k` doubles apart and its workspace block (identical internal layout) `ws`
 // doubles apart.  Single-chain entry points launch with one chain, the strides are then irrelevant.
-constexpr int MAX_CHAINS = 64;
 struct Chain {
     size_t k, ws;
 };
 struct ChainInts {
-    int v[MAX_CHAINS];
+    int v[SAMPLER_MAX_CHAINS];
 };
 struct ChainDoubles {
-    double v[MAX_CHAINS];
+    double v[SAMPLER_MAX_CHAINS];
 };
 
 // Y = K U for a skinny U (N x r), K row-major N x N, streamed once at HBM rate.
@@ -462,8 +461,8 @@ __global__ __launch_bounds__(LR_THREADS) void small_kernel(const double *__restr
             if (is_singular || (dec.accept_prev && dec.accept_prev[b] < 0)) {
                 acc = -1;
             } else {
-                const double log_alpha = dec.log_q_prior[b] + 0.5 * (q - logsum);
-                acc = (dec.log_u[b] <= log_alpha && dec.log_u[b] <= 0.0) ? 1 : 0;  // a NaN on either side compares false: reject
+                const double log_q = dec.log_q_prior[b], delta = 0.5 * (q - logsum);  // read and formed before log_u, as ever
+                acc = metropolis_accept(dec.log_u[b], log_q, delta);
             }
             dec.accept_out[b] = acc;
             if (acc > 0) {
@@ -700,11 +699,8 @@ void launch_rewrite(hipStream_t stream, const double *K, int N, int r, const dou
                        (const double *)nullptr, (const double *)nullptr);
 }
 
-// Metropolis decision of one tree proposal per chain on the device (bark_sampler.py:256-264):
-//   log_alpha = log_q_prior + (new_mll - cur_mll),  new_mll - cur_mll = 0.5 (dquad - dlogdet)   (scalars = {dquad, dlogdet})
-//   accept iff log(u) <= min(log_alpha, 0);  on accept the chain's running y'K^-1 y and log|K| move with it.
-//   (Python's min: a NaN log_alpha gives NaN and rejects.  fmin(NaN, 0) is 0 and would accept every such proposal, so the
-//   rule is written as two comparisons.)
+// Metropolis decision of one tree proposal per chain on the device (bark_sampler.py:256-264): metropolis_accept with new_mll -
+// cur_mll = 0.5 (dquad - dlogdet)  (scalars = {dquad, dlogdet}); on accept the chain's running y'K^-1 y and log|K| move with it.
 // accept_out: 1 / 0, or -1 when the r x r system was singular (the reference raises LinAlgError there).  A chain that
 // met a singular system stays at -1 for the rest of the sweep (accept_prev = the previous step's flags, null for the
 // first): its K_inv is not rewritten again, so K_inv, quad and logdet of that chain still belong together — the state
@@ -720,8 +716,8 @@ __global__ void decide_kernel(const double *__restrict__ scalars, const double *
     if (flags[(size_t)b * flag_stride_ints] != 0 || (accept_prev && accept_prev[b] < 0)) {
         acc = -1;
     } else {
-        const double log_alpha = log_q_prior[b] + 0.5 * (dquad - dlogdet);
-        acc = (log_u[b] <= log_alpha && log_u[b] <= 0.0) ? 1 : 0;  // a NaN on either side compares false: reject
+        const double log_q = log_q_prior[b], delta = 0.5 * (dquad - dlogdet);
+        acc = metropolis_accept(log_u[b], log_q, delta);
     }
     accept_out[b] = acc;
     if (acc > 0) {
@@ -934,7 +930,7 @@ int bark_tree_swap_eval_hip(bark_ctx *ctx, const double *K_inv, int64_t N, const
 // chain index is a grid dimension of every kernel (one launch sequence for all chains); otherwise one
 // single-chain sequence per chain, each on its own stream.
 size_t bark_tree_swap_chains_workspace_bytes(int64_t N, int64_t r, int64_t nc, size_t *chain_stride_bytes) {
-    if (N < 1 || r < 1 || r > LR_MAX || nc < 1 || nc > MAX_CHAINS) return 0;
+    if (N < 1 || r < 1 || r > LR_MAX || nc < 1 || nc > SAMPLER_MAX_CHAINS) return 0;
     const size_t stride = (size_t)round_up((int64_t)bark_tree_swap_workspace_bytes(N, r), 256);
     if (chain_stride_bytes) *chain_stride_bytes = stride;
     // nc per-chain blocks, then the one-hot codes of all chains, contiguous (one leaf walk for all of them)
@@ -1000,6 +996,8 @@ static int eval_chains(bark_ctx *ctx, const double *K_inv, int64_t N, int64_t nc
 
 extern "C" {
 
+int bark_debug_metropolis(double log_u, double log_q_prior, double mll_delta) { return metropolis_accept(log_u, log_q_prior, mll_delta); }
+
 int bark_tree_swap_eval_chains_hip(bark_ctx *ctx, const double *K_inv, int64_t N, int64_t nc, const void *packed,
                                    const bark_pack_info *info, const double *X, int64_t d, const int64_t *r_old,
                                    const double *s, const double *y, double *scalars_out, void *workspace,
@@ -1010,8 +1008,8 @@ int bark_tree_swap_eval_chains_hip(bark_ctx *ctx, const double *K_inv, int64_t N
         if (crc) return crc;
     }
     if (!K_inv || !packed || !info || !X || !r_old || !s || !y || !scalars_out || !workspace || N < 1 || d < 1 || nc < 1 ||
-        nc > MAX_CHAINS || N > (1 << 24))
-        return fail(BARK_ERR_ARG, "bark_tree_swap_eval_chains_hip: bad argument (1 <= chains <= %d)", MAX_CHAINS);
+        nc > SAMPLER_MAX_CHAINS || N > (1 << 24))
+        return fail(BARK_ERR_ARG, "bark_tree_swap_eval_chains_hip: bad argument (1 <= chains <= %d)", SAMPLER_MAX_CHAINS);
     if (info->B != nc || info->m != 2) return fail(BARK_ERR_ARG, "pack one [old tree, new tree] pair per chain (B = chains, m = 2)");
     const int64_t r = info->max_bits;
     if (r < 2 || r > LR_MAX) return fail(BARK_ERR_ARG, "tree swap supports 2..%d leaves in total (got %lld)", LR_MAX, (long long)r);
@@ -1045,8 +1043,8 @@ int bark_tree_sweep_chains_hip(bark_ctx *ctx, double *K_inv, int64_t N, int64_t 
         if (crc) return crc;
     }
     if (!K_inv || !packed || !packed_offsets || !infos || !X || !r_old || !s || !y || !log_q_prior || !log_u || !state ||
-        !accept_out || !workspace || N < 1 || d < 1 || nc < 1 || nc > MAX_CHAINS || n_steps < 1 || N > (1 << 24))
-        return fail(BARK_ERR_ARG, "bark_tree_sweep_chains_hip: bad argument (1 <= chains <= %d)", MAX_CHAINS);
+        !accept_out || !workspace || N < 1 || d < 1 || nc < 1 || nc > SAMPLER_MAX_CHAINS || n_steps < 1 || N > (1 << 24))
+        return fail(BARK_ERR_ARG, "bark_tree_sweep_chains_hip: bad argument (1 <= chains <= %d)", SAMPLER_MAX_CHAINS);
     int64_t r_max = 0;
     for (int64_t t = 0; t < n_steps; ++t) {
         const bark_pack_info &in = infos[t];
@@ -1093,7 +1091,7 @@ int bark_tree_sweep_chains_hip(bark_ctx *ctx, double *K_inv, int64_t N, int64_t 
 int bark_lowrank_swap_apply_chains_hip(double *K_inv, int64_t N, int64_t nc, int64_t r, const int32_t *accept,
                                        void *workspace, size_t workspace_bytes, void *stream_) {
     error_buffer()[0] = 0;
-    if (!K_inv || !accept || !workspace || N < 1 || nc < 1 || nc > MAX_CHAINS || r < 1 || r > LR_MAX)
+    if (!K_inv || !accept || !workspace || N < 1 || nc < 1 || nc > SAMPLER_MAX_CHAINS || r < 1 || r > LR_MAX)
         return fail(BARK_ERR_ARG, "bark_lowrank_swap_apply_chains_hip: bad argument");
     size_t stride = 0;
     if (workspace_bytes < bark_tree_swap_chains_workspace_bytes(N, r, nc, &stride))

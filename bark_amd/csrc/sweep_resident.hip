@@ -21,19 +21,18 @@
 // Z overlays the X rows / codes / nodes / r x r scratch, all dead by then; the X rows are staged again after a rewrite.
 #include <type_traits>
 
-#include "common.h"
+#include "sampler_step.h"  // -> common.h
 
 namespace bark {
 namespace {
 
 constexpr int SR_THREADS = 1024, SR_WAVES = SR_THREADS / 64;
 constexpr int SR_RMAX = 16;                   // leaves per [old, new] pair: one 16-bit code per point
-constexpr int SR_NMAX = 512, SR_CHAINS = 64;
+constexpr int SR_NMAX = 512;
 constexpr int SR_NODE_BYTES = 2048;           // LDS of a step's packed pair: at most 64 packed nodes per tree (a tree of <= 15 leaves has <= 29)
 constexpr int SR_STRIDE_MAX = SR_NODE_BYTES / (2 * 16);
 constexpr int SR_AUG_LD = 2 * SR_RMAX + 1;    // [den | I], odd pitch
 constexpr size_t SR_LDS_MAX = 160 * 1024;
-constexpr int SR_TABLE_WORDS = 4;             // per step: offset, stride, max_depth, r
 
 // dynamic-LDS layout (bytes from the base; every offset a multiple of 16) and the variant, from the shape alone
 struct SrPlan {
@@ -76,14 +75,6 @@ struct SrArgs {
     int32_t *accept_out, *fault;
     SrPlan plan;
 };
-
-// the waves of a workgroup other than the one running the r x r algebra wait at the next barrier; inside that wave LDS
-// traffic is ordered by the fence (s_waitcnt) and the lanes run in lock step
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
 
 template <bool K_IN_LDS>
 __global__ __launch_bounds__(SR_THREADS) void sweep_resident_kernel(SrArgs p) {
@@ -142,11 +133,9 @@ __global__ __launch_bounds__(SR_THREADS) void sweep_resident_kernel(SrArgs p) {
             if (tid == 0) p.accept_out[(size_t)t * nc + b] = -1;
             continue;
         }
-        const int64_t *hd = p.table + (size_t)t * SR_TABLE_WORDS;
-        const int stride = min(max((int)hd[1], 1), SR_STRIDE_MAX), max_depth = (int)hd[2];  // the table builder checked; never overrun LDS
-        const int r = min(max((int)hd[3], 2), SR_RMAX);
-        const int r_old = min(max((int)p.table[(size_t)p.n_steps * SR_TABLE_WORDS + (size_t)t * nc + b], 1), r - 1);
-        const uint4 *pair = reinterpret_cast<const uint4 *>(p.packed + hd[0]) + (size_t)b * 2 * stride;
+        const StepEntry st = step_entry(p.table, t, p.n_steps, nc, b, SR_STRIDE_MAX);
+        const int stride = st.stride, max_depth = st.max_depth, r = min(max(st.word3, 2), SR_RMAX), r_old = min(max(st.column, 1), r - 1);
+        const uint4 *pair = reinterpret_cast<const uint4 *>(p.packed + st.offset) + (size_t)b * 2 * stride;
 
         // ---- 1. walk ----
         for (int e = tid; e < 2 * stride; e += SR_THREADS) ln[e] = pair[e];
@@ -269,9 +258,7 @@ __global__ __launch_bounds__(SR_THREADS) void sweep_resident_kernel(SrArgs p) {
                 if (is_singular) {
                     acc = -1;
                 } else {
-                    const double log_alpha = p.log_q_prior[at] + 0.5 * (q - logsum);
-                    const double lu = p.log_u[at];
-                    acc = (lu <= log_alpha && lu <= 0.0) ? 1 : 0;  // a NaN on either side compares false: reject
+                    acc = metropolis_accept(p.log_u[at], p.log_q_prior[at], 0.5 * (q - logsum));
                 }
                 p.accept_out[at] = acc;
                 if (acc > 0) {
@@ -371,8 +358,8 @@ __global__ __launch_bounds__(SR_THREADS) void sweep_resident_kernel(SrArgs p) {
 int sr_check_shape(int64_t N, int64_t nc, int64_t d, SrPlan *plan) {
     if (N < 1 || N > SR_NMAX)
         return fail(BARK_ERR_ARG, "one-launch sweep: N = %lld is outside 1..%d" SR_USE_OTHER, (long long)N, SR_NMAX);
-    if (nc < 1 || nc > SR_CHAINS)
-        return fail(BARK_ERR_ARG, "one-launch sweep: %lld chains are outside 1..%d" SR_USE_OTHER, (long long)nc, SR_CHAINS);
+    if (nc < 1 || nc > SAMPLER_MAX_CHAINS)
+        return fail(BARK_ERR_ARG, "one-launch sweep: %lld chains are outside 1..%d" SR_USE_OTHER, (long long)nc, SAMPLER_MAX_CHAINS);
     if (d < 1) return fail(BARK_ERR_ARG, "one-launch sweep: d = %lld" SR_USE_OTHER, (long long)d);
     *plan = sr_plan(N, d);
     if (plan->variant == 0)
@@ -389,8 +376,8 @@ using namespace bark;
 extern "C" {
 
 size_t bark_tree_sweep_resident_table_bytes(int64_t n_steps, int64_t nc) {
-    if (n_steps < 1 || nc < 1 || nc > SR_CHAINS || n_steps > ((int64_t)1 << 32)) return 0;
-    return (size_t)(n_steps * (SR_TABLE_WORDS + nc)) * sizeof(int64_t);
+    if (n_steps < 1 || nc < 1 || nc > SAMPLER_MAX_CHAINS || n_steps > ((int64_t)1 << 32)) return 0;
+    return (size_t)(n_steps * (STEP_TABLE_WORDS + nc)) * sizeof(int64_t);
 }
 
 int bark_tree_sweep_resident_table(const int64_t *packed_offsets, const bark_pack_info *infos, const int64_t *r_old,
@@ -398,38 +385,26 @@ int bark_tree_sweep_resident_table(const int64_t *packed_offsets, const bark_pac
     error_buffer()[0] = 0;
     if (!packed_offsets || !infos || !r_old || !table_host_out || n_steps < 1 || n_steps > ((int64_t)1 << 32))
         return fail(BARK_ERR_ARG, "bark_tree_sweep_resident_table: bad argument");
-    if (nc < 1 || nc > SR_CHAINS)
-        return fail(BARK_ERR_ARG, "one-launch sweep: %lld chains are outside 1..%d" SR_USE_OTHER, (long long)nc, SR_CHAINS);
+    if (nc < 1 || nc > SAMPLER_MAX_CHAINS)
+        return fail(BARK_ERR_ARG, "one-launch sweep: %lld chains are outside 1..%d" SR_USE_OTHER, (long long)nc, SAMPLER_MAX_CHAINS);
+    const StepPackRule rule{"one-launch sweep", "one [old, new] pair", " fit LDS" SR_USE_OTHER, 2, SR_STRIDE_MAX, true};
     for (int64_t t = 0; t < n_steps; ++t) {
         const bark_pack_info &in = infos[t];
-        if (in.B != nc || in.m != 2)
-            return fail(BARK_ERR_ARG, "step %lld: pack one [old, new] pair per chain (B = chains, m = 2)", (long long)t);
+        if (step_pack_check(rule, t, packed_offsets[t], in, nc)) return BARK_ERR_ARG;
         if (in.max_bits < 2 || in.max_bits > SR_RMAX)
             return fail(BARK_ERR_ARG, "one-launch sweep, step %lld: %lld leaves in a pair are outside 2..%d" SR_USE_OTHER, (long long)t,
                         (long long)in.max_bits, SR_RMAX);
-        if (in.stride > SR_STRIDE_MAX)
-            return fail(BARK_ERR_ARG, "one-launch sweep, step %lld: %lld packed nodes in a tree, at most %d fit LDS" SR_USE_OTHER, (long long)t,
-                        (long long)in.stride, SR_STRIDE_MAX);
-        if (packed_offsets[t] < 0 || packed_offsets[t] % 16 != 0 || in.stride < 1 || in.max_depth < 0 || in.max_depth > (1 << 24))
-            return fail(BARK_ERR_ARG, "step %lld: bad offset, stride or depth", (long long)t);
         for (int64_t b = 0; b < nc; ++b)
             if (r_old[t * nc + b] < 1 || r_old[t * nc + b] >= in.max_bits)
                 return fail(BARK_ERR_ARG, "step %lld chain %lld: r_old = %lld is not inside (0, %lld)", (long long)t, (long long)b,
                             (long long)r_old[t * nc + b], (long long)in.max_bits);
     }
-    int64_t *out = static_cast<int64_t *>(table_host_out);
-    for (int64_t t = 0; t < n_steps; ++t) {
-        out[t * SR_TABLE_WORDS + 0] = packed_offsets[t];
-        out[t * SR_TABLE_WORDS + 1] = infos[t].stride;
-        out[t * SR_TABLE_WORDS + 2] = infos[t].max_depth;
-        out[t * SR_TABLE_WORDS + 3] = infos[t].max_bits;
-    }
-    for (int64_t e = 0; e < n_steps * nc; ++e) out[n_steps * SR_TABLE_WORDS + e] = r_old[e];
+    step_table_write(static_cast<int64_t *>(table_host_out), packed_offsets, infos, nullptr, r_old, n_steps, nc);
     return BARK_OK;
 }
 
 size_t bark_tree_sweep_resident_workspace_bytes(int64_t N, int64_t r_max, int64_t nc) {
-    if (N < 1 || N > SR_NMAX || r_max < 2 || r_max > SR_RMAX || nc < 1 || nc > SR_CHAINS) return 0;
+    if (N < 1 || N > SR_NMAX || r_max < 2 || r_max > SR_RMAX || nc < 1 || nc > SAMPLER_MAX_CHAINS) return 0;
     return 256;  // everything the kernel needs sits in LDS
 }
 

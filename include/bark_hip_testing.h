@@ -35,6 +35,10 @@ typedef struct {
 int bark_frontend_variant_query(const bark_pack_info *info, int64_t N, int64_t M, int64_t d, int64_t ld, int64_t batch_stride,
                                 int out_mod16, bark_frontend_variant *out);
 
+/* The sampler's Metropolis decision as every device path takes it (metropolis_accept, csrc/sampler_step.h), evaluated on the
+ * host: 1 accept, 0 reject, for log(u), log_q_prior and new_mll - cur_mll.  Pure host code, NOT gated by $BARK_TEST_HOOKS. */
+int bark_debug_metropolis(double log_u, double log_q_prior, double mll_delta);
+
 #ifdef __cplusplus
 }
 #endif
