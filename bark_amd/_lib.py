@@ -154,7 +154,17 @@ SIGNATURES = {
     "bark_acquisition_scan_targets_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64, i64, i64]),
     "bark_acquisition_scan_targets_hip": (ci, [vp, vp, ctypes.POINTER(PackInfo), vp, i64, i64, vp, vp, vp, vp, i64, vp, i64, vp, i64,
                                                vp, i64, ctypes.c_double, ci, ci, vp, vp, vp, vp, vp, ctypes.c_size_t, i64, vp]),
-    "bark_predictive_scores_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64, i64]),
+    "bark_leaf_posterior_bytes": (ctypes.c_size_t, [i64, i64, i64]),
+    "bark_leaf_posterior_fit_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64]),
+    "bark_leaf_posterior_fit_hip": (ci, [vp, vp, ctypes.POINTER(PackInfo), vp, i64, i64, vp, vp, vp, vp, ctypes.c_size_t, vp, vp,
+                                         ctypes.c_size_t, i64, vp]),
+    "bark_acquisition_scan_fitted_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64, i64, ci]),
+    "bark_acquisition_scan_fitted_hip": (ci, [vp, vp, ctypes.POINTER(PackInfo), i64, vp, vp, vp, ctypes.c_size_t, vp, i64, vp, i64,
+                                              vp, i64, vp, i64, ctypes.c_double, ci, ci, vp, vp, vp, vp, vp, ctypes.c_size_t, i64, vp]),
+    "bark_leaf_posterior_condition_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64]),
+    "bark_leaf_posterior_condition_hip": (ci, [vp, vp, ctypes.POINTER(PackInfo), i64, vp, vp, vp, i64, vp, ctypes.c_size_t, vp, vp,
+                                               ctypes.c_size_t, i64, vp]),
+    "bark_predictive_scores_workspace_bytes":(ctypes.c_size_t, [i64, i64, i64, i64, i64]),
     "bark_predictive_scores_hip": (ci, [vp, vp, ctypes.POINTER(PackInfo), vp, i64, i64, vp, vp, vp, vp, i64, vp, ci, ci, vp, vp, vp,
                                         vp, vp, ctypes.c_size_t, i64, vp]),
     "bark_lowrank_workspace_bytes": (ctypes.c_size_t, [i64, i64]),

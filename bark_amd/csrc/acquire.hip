@@ -7,6 +7,7 @@
 //     var_b(x) = (scale_b / m) * ( sum_i Minv[a_i][a_i] + 2 * sum_i ( sum_{j < i} Minv[a_j][a_i] ) )
 // Only the upper triangle of M^-1 is read, m (m + 1) / 2 entries instead of leaf_predict_kernel's m^2.  The kernels:
 //   acq_condition_kernel  optional: M^-1 conditioned on the pending points (rank-one downdates), before anything reads it
+//   acq_condition_from_kernel  the same out of place, for the scan from a fitted state (the state is only read)
 //   acq_pack_kernel     upper triangle of M^-1, rows packed, followed by w: the image acq_scan_kernel stages in LDS
 //   acq_scan_kernel     one thread per candidate; the forests of the chunk in order, three running sums per candidate in
 //                       registers (sum of mu - kappa sd, of mu, of var + mu^2), kept in a (3, C) buffer between chunks
@@ -94,6 +95,70 @@ __global__ __launch_bounds__(ACQ_COND_THREADS) void acq_condition_kernel(const u
             const double ti = t[i];
             double *row = Mb + (size_t)i * R;
             for (int j = lane; j < R; j += 64) row[j] -= g * (ti * t[j]);
+        }
+        __syncthreads();  // the next point reads the updated matrix and reuses t and the leaf list
+    }
+}
+
+// The same conditioning out of place, for a scan that starts from a fitted state it must not modify (leafsystem.hip,
+// bark_acquisition_scan_fitted_hip): the first point reads `src` (the state's M^-1) and writes `dst` (scratch of the call),
+// the later points run in place on `dst`.  P >= 1.  Every product, sum and their order are acq_condition_kernel's, so `dst`
+// ends with the bits that kernel leaves in a matrix that started as `src`.  A forest whose sweep failed is copied as it is:
+// the scan still reads it (its result is NaN / -1 through acq_best_kernel).  Same LDS layout; src and dst do not overlap.
+__global__ __launch_bounds__(ACQ_COND_THREADS) void acq_condition_from_kernel(const uint32_t *__restrict__ pcodes, int W, int ppad,
+                                                                              int P, const double *src, double *dst, int R,
+                                                                              const double *__restrict__ noise,
+                                                                              const double *__restrict__ scale, int m,
+                                                                              const int32_t *__restrict__ info) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+    const double *Sb = src + (size_t)b * R * R;
+    double *Db = dst + (size_t)b * R * R;
+    if (info[b] != 0) {  // the whole workgroup: no barrier is left waiting
+        for (size_t e = tid; e < (size_t)R * R; e += ACQ_COND_THREADS) Db[e] = Sb[e];
+        return;
+    }
+    double *t = smem;
+    double *qs = smem + R;
+    int *leaves = reinterpret_cast<int *>(smem + R + 1);
+    int *count = leaves + ACQ_MAX_TREES;
+    const double c = scale[b] / ((double)m * (1e-6 + noise[b]));
+    for (int p = 0; p < P; ++p) {
+        const double *Mb = p == 0 ? Sb : Db;  // what this point reads; it writes Db
+        if (tid == 0) {
+            int cnt = 0;
+            for (int w0 = 0; w0 < W; ++w0) {
+                uint32_t bits = pcodes[((size_t)b * W + w0) * ppad + p];
+                while (bits) {  // bits in increasing order: tree order
+                    const int a = 32 * w0 + __builtin_ctz(bits);
+                    if (cnt < ACQ_MAX_TREES && a < R) leaves[cnt++] = a;
+                    bits &= bits - 1;
+                }
+            }
+            *count = cnt;
+        }
+        __syncthreads();
+        const int cnt = *count;
+        for (int i = tid; i < R; i += ACQ_COND_THREADS) {
+            const double *row = Mb + (size_t)i * R;
+            double s = 0.0;
+            for (int k = 0; k < cnt; ++k) s += row[leaves[k]];
+            t[i] = s;
+        }
+        __syncthreads();
+        if (wave == 0) {
+            double v = lane < cnt ? t[leaves[lane]] : 0.0;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+            if (lane == 0) *qs = v;
+        }
+        __syncthreads();
+        const double g = c / (1.0 + c * *qs);
+        for (int i = wave; i < R; i += ACQ_COND_THREADS / 64) {
+            const double ti = t[i];
+            const double *in = Mb + (size_t)i * R;
+            double *out = Db + (size_t)i * R;
+            for (int j = lane; j < R; j += 64) out[j] = in[j] - g * (ti * t[j]);
         }
         __syncthreads();  // the next point reads the updated matrix and reuses t and the leaf list
     }
@@ -312,7 +377,8 @@ int raise_acq_lds_limits() {
                                       {reinterpret_cast<const void *>(scan_kernel(true, BARK_ACQ_EI)), ACQ_LDS_MAX},
                                       {reinterpret_cast<const void *>(scan_kernel(true, BARK_ACQ_PI)), ACQ_LDS_MAX},
                                       {reinterpret_cast<const void *>(scan_kernel(true, BARK_ACQ_MES)), ACQ_LDS_MAX},
-                                      {reinterpret_cast<const void *>(acq_condition_kernel), acq_condition_lds_bytes(8192)}};
+                                      {reinterpret_cast<const void *>(acq_condition_kernel), acq_condition_lds_bytes(8192)},
+                                      {reinterpret_cast<const void *>(acq_condition_from_kernel), acq_condition_lds_bytes(8192)}};
     static LdsLimitsOnce once;
     return raise_lds_limits(once, limits);
 }
@@ -333,6 +399,17 @@ int acq_condition(const uint32_t *pcodes, int W, int ppad, int P, double *Minv, 
     if (rc) return rc;
     hipLaunchKernelGGL(acq_condition_kernel, dim3((unsigned)bc), dim3(ACQ_COND_THREADS), acq_condition_lds_bytes(R), s, pcodes, W,
                        ppad, P, Minv, R, noise, scale, m, info);
+    BARK_LAUNCH_CHECK();
+    return BARK_OK;
+}
+
+// ... out of place: dst = src conditioned on the P >= 1 points; src is only read
+int acq_condition_from(const uint32_t *pcodes, int W, int ppad, int P, const double *src, double *dst, int R, const double *noise,
+                       const double *scale, int m, int bc, const int32_t *info, hipStream_t s) {
+    const int rc = raise_acq_lds_limits();
+    if (rc) return rc;
+    hipLaunchKernelGGL(acq_condition_from_kernel, dim3((unsigned)bc), dim3(ACQ_COND_THREADS), acq_condition_lds_bytes(R), s, pcodes,
+                       W, ppad, P, src, dst, R, noise, scale, m, info);
     BARK_LAUNCH_CHECK();
     return BARK_OK;
 }

@@ -168,6 +168,9 @@ size_t acq_table_doubles(int64_t R);
 // M^-1 of the chunk's forests conditioned on the P pending points whose codes are pcodes (bc, W, ppad)
 int acq_condition(const uint32_t *pcodes, int W, int ppad, int P, double *Minv, int R, const double *noise, const double *scale,
                   int m, int bc, const int32_t *info, hipStream_t s);
+// ... out of place (P >= 1): dst (bc, R, R) = src conditioned; src, e.g. a fitted state, is only read
+int acq_condition_from(const uint32_t *pcodes, int W, int ppad, int P, const double *src, double *dst, int R, const double *noise,
+                       const double *scale, int m, int bc, const int32_t *info, hipStream_t s);
 // image of the chunk for the LDS variant
 int acq_pack(const double *Minv, const double *w, int R, int bc, double *tab, hipStream_t s);
 // variant: 1 LDS, 2 global (resolved by bark_acquisition_plan); n candidates of one slab against the bc forests of the chunk;

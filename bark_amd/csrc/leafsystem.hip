@@ -4,13 +4,19 @@
 // entry point checks its own arguments, says what it keeps in the workspace (LeafNeeds), opens the system and hands
 // for_chunks a body that lists the steps it takes.
 // The kernels are elsewhere: the R x R Cholesky sweep in chol.hip (reached through SystemSweep, common.h), the leaf-space
-// kernels in leafspace.hip, sample.hip, acquire.hip and scores.hip; this unit's only kernel is fault_info_kernel.
+// kernels in leafspace.hip, sample.hip, acquire.hip and scores.hip; this unit's only kernels move status words
+// (fault_info_kernel, copy_info_kernel).
+// A fitted posterior (bark_leaf_posterior_*_hip, bark_acquisition_scan_fitted_hip) is the part of that state which outlives
+// a call: M^-1, w and the sweep's status of all B forests in a buffer of the caller's (PosteriorState).
 #include <cmath>
 
 #include "sampler_step.h"  // -> common.h
 
 namespace bark {
 namespace {
+
+constexpr int64_t ACQ_SLAB = 1 << 16;  // candidates walked and scanned per launch pair: bounds the code buffer (Bc, W, slab)
+constexpr int64_t ACQ_MAX_PENDING = 64, ACQ_MAX_SKIP = 64, ACQ_MAX_TARGETS = 1024;
 
 // what a call keeps in its workspace besides the R x R sweep's own areas, the leaf codes of the N points and y'y
 struct LeafNeeds {
@@ -90,8 +96,6 @@ LeafAreas leaf_areas(void *workspace, int64_t N, int64_t R, int64_t m, int64_t B
     return a;
 }
 
-constexpr int64_t ACQ_SLAB = 1 << 16;  // candidates walked and scanned per launch pair: bounds the code buffer (Bc, W, slab)
-
 LeafNeeds mll_needs(int64_t C) {  // MLL; posterior at C candidates from w and M^-1
     LeafNeeds q;
     q.cand = C;
@@ -110,12 +114,15 @@ LeafNeeds samples_needs(int64_t C, int64_t S) {  // draws need V and w, not M^-1
     q.S = S;
     return q;
 }
-constexpr int64_t ACQ_MAX_PENDING = 64, ACQ_MAX_SKIP = 64, ACQ_MAX_TARGETS = 1024;
-
 LeafNeeds scan_needs(int64_t C, int64_t P) {  // the posterior's areas with the codes of one slab of candidates
     LeafNeeds q = mll_needs(C < ACQ_SLAB ? C : ACQ_SLAB);
     q.scan = C;
     q.pending = P;
+    return q;
+}
+LeafNeeds fit_needs() {  // the sweep with the identity columns; w and M^-1 go straight into the caller's state
+    LeafNeeds q;
+    q.identity = true;
     return q;
 }
 LeafNeeds scores_needs(int64_t C) {  // the scan's areas (its three sums per point hold the mixture's state) and the tile partials
@@ -134,6 +141,109 @@ __global__ void fault_info_kernel(const int32_t *fault, int32_t *info, int Bc) {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < Bc && *fault) info[b] = -1;
 }
+
+// status words from one place to another (a fitted state's and a call's info_out)
+__global__ void copy_info_kernel(const int32_t *__restrict__ src, int32_t *__restrict__ dst, int n) {
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b < n) dst[b] = src[b];
+}
+
+// A fitted posterior in a buffer of the caller's: M^-1 (B, R, R), w (B, R), then the sweep's status per forest, each area
+// 256-byte aligned.  bark_leaf_posterior_bytes and the entry points get sizes and pointers here.  base == nullptr: sizes only.
+struct PosteriorState {
+    double *Minv, *w;
+    int32_t *info;
+    size_t total;
+};
+PosteriorState posterior_state(void *base, int64_t R, int64_t B) {
+    Carve cv{static_cast<char *>(base)};
+    PosteriorState st;
+    st.Minv = cv.take<double>((size_t)B * R * R);
+    st.w = cv.take<double>((size_t)B * R);
+    st.info = cv.take<int32_t>((size_t)B);
+    st.total = cv.o;
+    return st;
+}
+bool posterior_shape_ok(int64_t R, int64_t m, int64_t B) { return R >= 1 && R <= 8192 && m >= 1 && m <= ACQ_MAX_TREES && B >= 1; }
+
+// The workspace of the calls that start from a fitted state (nothing of size N): the codes of one slab of candidates and of
+// the pending points for Bc forests, the LDS image when that variant runs, the scan's sums and partials, and the scratch
+// M^-1 that the pending points are conditioned into.  C == 0: conditioning only.
+struct FittedAreas {
+    int64_t W, cpad, ppad;
+    uint32_t *ccodes, *pcodes;
+    double *tab, *acc, *part, *Minv;
+    int64_t *part_i;
+    size_t total;
+};
+FittedAreas fitted_areas(void *workspace, int64_t R, int64_t Bc, int64_t C, int64_t P, bool lds_table, bool scratch) {
+    FittedAreas a;
+    a.W = (R + 31) / 32;
+    a.cpad = C > 0 ? round_up(C < ACQ_SLAB ? C : ACQ_SLAB, TILE) : 0;
+    a.ppad = P > 0 ? round_up(P, TILE) : 0;
+    const size_t nb = (size_t)Bc, partials = C > 0 ? acq_partials(C) : 0;
+    Carve cv{static_cast<char *>(workspace)};
+    a.ccodes = cv.take<uint32_t>(nb * a.W * a.cpad);
+    a.pcodes = cv.take<uint32_t>(nb * a.W * a.ppad);
+    a.tab = cv.take<double>(lds_table ? nb * acq_table_doubles(R) : 0);
+    a.acc = cv.take<double>((size_t)3 * C);
+    a.part = cv.take<double>(partials);
+    a.part_i = cv.take<int64_t>(partials);
+    a.Minv = cv.take<double>(scratch && P > 0 ? nb * R * R : 0);
+    a.total = cv.o;
+    return a;
+}
+
+// What the calls on a fitted state share: the checks (nothing is launched before a refusal), the state's areas, the chunk
+// size.  They factorise nothing, so there is no sweep and no LeafSystem.
+struct FittedCall {
+    bark_ctx *ctx = nullptr;
+    hipStream_t caller = nullptr;
+    const void *packed = nullptr;
+    const bark_pack_info *info = nullptr;
+    int64_t d = 0, B = 0, Bc = 0;
+    int m = 0, R = 0;
+    PosteriorState st{};
+
+    int open(const char *name, bark_ctx *ctx_, const void *packed_, const bark_pack_info *info_, int64_t d_, const double *noise,
+             const double *scale, const void *state, size_t state_bytes, const void *info_out, const void *workspace, int64_t Bc_,
+             void *stream) {
+        int rc = check_ctx(ctx_);
+        if (rc) return rc;
+        if (!packed_ || !info_ || !noise || !scale || !state || !info_out || !workspace) return fail(BARK_ERR_ARG, "%s: null argument", name);
+        ctx = ctx_, packed = packed_, info = info_, d = d_, B = info->B, Bc = Bc_;
+        if (d < 1 || B < 1 || Bc < 1) return fail(BARK_ERR_ARG, "%s: bad shape d=%lld B=%lld Bc=%lld", name, (long long)d, (long long)B, (long long)Bc);
+        if (!posterior_shape_ok(info->max_bits, info->m, B))
+            return fail(BARK_ERR_ARG, "%s: a fitted posterior holds forests of at most %d trees and 8192 leaves (got m = %lld, R = %lld)", name,
+                        ACQ_MAX_TREES, (long long)info->m, (long long)info->max_bits);
+        if (Bc > B) Bc = B;
+        if (Bc > 65535) Bc = 65535;
+        m = (int)info->m, R = (int)info->max_bits;
+        st = posterior_state(const_cast<void *>(state), R, B);
+        if (state_bytes < st.total) return fail(BARK_ERR_ARG, "%s: state buffer too small: %zu < %zu bytes", name, state_bytes, st.total);
+        if ((reinterpret_cast<uintptr_t>(state) | reinterpret_cast<uintptr_t>(workspace)) & 255)
+            return fail(BARK_ERR_ARG, "%s: state and workspace must be 256-byte aligned", name);
+        caller = static_cast<hipStream_t>(stream);
+        return BARK_OK;
+    }
+    // the forests c0 .. c0 + n - 1 as a pack of their own, for the leaf walks
+    const char *chunk(int64_t c0, int64_t n, bark_pack_info &sub) const {
+        sub = *info;
+        sub.B = n;
+        return static_cast<const char *>(packed) + (size_t)c0 * m * info->stride * 16;
+    }
+    int copy_info(const int32_t *src, int32_t *dst, int n) const {
+        hipLaunchKernelGGL(copy_info_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, caller, src, dst, n);
+        BARK_LAUNCH_CHECK();
+        return BARK_OK;
+    }
+    // an invalid categorical value met by a walk of this call goes into these status words
+    int fault_info(int32_t *dst, int n) const {
+        hipLaunchKernelGGL(fault_info_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, caller, ctx->fault, dst, n);
+        BARK_LAUNCH_CHECK();
+        return BARK_OK;
+    }
+};
 
 struct LeafSystem {
     bark_ctx *ctx = nullptr;
@@ -220,10 +330,12 @@ struct LeafSystem {
     // w = M^-1 v = V'z from the swept chunk (the kernel of the dense posterior mean)
     int solve_w() { return system_sweep_w(sw, a.w); }
     // ... and M^-1 = V'V (the kernel of the dense inverse export)
-    int solve_w_minv() {
-        const int rc = solve_w();
+    int solve_w_minv() { return solve_w_minv_into(a.w, a.Minv); }
+    // the same two launches with the chunk's outputs (bc, R) and (bc, R, R) somewhere else: a fitted state
+    int solve_w_minv_into(double *w, double *Minv) {
+        const int rc = system_sweep_w(sw, w);
         if (rc) return rc;
-        return system_sweep_minv(sw, a.Minv);
+        return system_sweep_minv(sw, Minv);
     }
     // one-hot codes of n candidates (at most LeafNeeds::cand) under the chunk's forests -> a.ccodes
     int walk_candidates(const double *cand, int64_t n) {
@@ -459,6 +571,151 @@ int bark_acquisition_scan_hip(bark_ctx *ctx, const void *packed, const bark_pack
                               int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc, void *stream_) {
     return bark_acquisition_scan_pending_hip(ctx, packed, info, X, N, d, y, noise, scale, cand, C, nullptr, 0, nullptr, 0, kappa, kind,
                                              variant, acq_out, best_out, idx_out, info_out, workspace, workspace_bytes, Bc, stream_);
+}
+
+// ---- fitted posterior (include/bark_hip.h): fit once, scan and condition from the state ----
+
+size_t bark_leaf_posterior_bytes(int64_t max_bits, int64_t m, int64_t B) {
+    if (!posterior_shape_ok(max_bits, m, B)) return 0;
+    return posterior_state(nullptr, max_bits, B).total;
+}
+
+size_t bark_leaf_posterior_fit_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t Bc) {
+    if (N < 1 || Bc < 1 || !posterior_shape_ok(max_bits, m, 1)) return 0;
+    return leaf_areas(nullptr, N, max_bits, m, Bc, fit_needs()).total;
+}
+
+size_t bark_acquisition_scan_fitted_workspace_bytes(int64_t max_bits, int64_t m, int64_t Bc, int64_t C, int64_t P, int variant) {
+    int var = 0;
+    if (Bc < 1 || C < 1 || C > (1 << 24) || P < 0 || P > ACQ_MAX_PENDING || bark_acquisition_plan(max_bits, m, variant, &var, nullptr)) {
+        error_buffer()[0] = 0;  // a query reports through its value only
+        return 0;
+    }
+    return fitted_areas(nullptr, max_bits, Bc, C, P, var == 1, true).total;
+}
+
+size_t bark_leaf_posterior_condition_workspace_bytes(int64_t max_bits, int64_t m, int64_t Bc, int64_t P) {
+    if (Bc < 1 || P < 0 || P > ACQ_MAX_PENDING || !posterior_shape_ok(max_bits, m, 1)) return 0;
+    return fitted_areas(nullptr, max_bits, Bc, 0, P, false, false).total;
+}
+
+// The opening sequence of the scan, chunk by chunk, with the sweep's two outputs and its status pointed into the state: no
+// copy.  The status words reach info_out once, after the last chunk.
+int bark_leaf_posterior_fit_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d,
+                                const double *y, const double *noise, const double *scale, void *state, size_t state_bytes,
+                                int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc, void *stream_) {
+    error_buffer()[0] = 0;
+    if (!info || !scale || !state) return fail(BARK_ERR_ARG, "bark_leaf_posterior_fit_hip: null argument");
+    int rc;
+    if ((rc = bark_acquisition_plan(info->max_bits, info->m, 0, nullptr, nullptr))) return rc;
+    if (info->B < 1) return fail(BARK_ERR_ARG, "bark_leaf_posterior_fit_hip: bad shape B=%lld", (long long)info->B);
+    const PosteriorState st = posterior_state(state, info->max_bits, info->B);
+    if (state_bytes < st.total)
+        return fail(BARK_ERR_ARG, "bark_leaf_posterior_fit_hip: state buffer too small: %zu < %zu bytes", state_bytes, st.total);
+    if (reinterpret_cast<uintptr_t>(state) & 255) return fail(BARK_ERR_ARG, "bark_leaf_posterior_fit_hip: state must be 256-byte aligned");
+    LeafSystem sys;
+    rc = sys.open("bark_leaf_posterior_fit_hip", ctx, packed, info, X, N, d, y, noise, info_out, workspace, workspace_bytes, Bc, 0,
+                  fit_needs(), stream_);
+    if (rc) return rc;
+    const size_t R = (size_t)sys.R;
+    rc = sys.for_chunks([&](int64_t c0) -> int {
+        int r = sys.factor_chunk(noise + c0, scale + c0, st.info + c0, nullptr, 0);
+        if (r || (r = sys.solve_w_minv_into(st.w + (size_t)c0 * R, st.Minv + (size_t)c0 * R * R))) return r;
+        return sys.close_chunk();
+    });
+    if (rc) return rc;
+    hipLaunchKernelGGL(copy_info_kernel, dim3((unsigned)((sys.B + 255) / 256)), dim3(256), 0, sys.caller, st.info, info_out, (int)sys.B);
+    BARK_LAUNCH_CHECK();
+    return BARK_OK;
+}
+
+// The scan of bark_acquisition_scan_targets_hip from its `P > 0` on, with M^-1 and w read from the state.  The state is only
+// read: pending points condition a copy of the chunk's M^-1 in the workspace (acq_condition_from_kernel).  info_out starts
+// as the state's status and takes the faults of this call's walks.
+int bark_acquisition_scan_fitted_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, int64_t d, const double *noise,
+                                     const double *scale, const void *state, size_t state_bytes, const double *cand, int64_t C,
+                                     const double *pending, int64_t P, const int64_t *skip_idx, int64_t n_skip, const double *targets,
+                                     int64_t S, double kappa, int kind, int variant, double *acq_out, double *best_out,
+                                     int64_t *idx_out, int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc,
+                                     void *stream_) {
+    static const char *name = "bark_acquisition_scan_fitted_hip";
+    error_buffer()[0] = 0;
+    if (!info || !cand || !best_out || !idx_out) return fail(BARK_ERR_ARG, "%s: null argument", name);
+    if (C < 1 || C > (1 << 24)) return fail(BARK_ERR_ARG, "%s: bad shape C=%lld", name, (long long)C);
+    if (P < 0 || P > ACQ_MAX_PENDING || n_skip < 0 || n_skip > ACQ_MAX_SKIP)
+        return fail(BARK_ERR_ARG, "%s: at most %lld pending points and %lld skipped candidates (got %lld, %lld)", name,
+                    (long long)ACQ_MAX_PENDING, (long long)ACQ_MAX_SKIP, (long long)P, (long long)n_skip);
+    if ((P > 0 && !pending) || (n_skip > 0 && !skip_idx)) return fail(BARK_ERR_ARG, "%s: null argument", name);
+    if (kind < BARK_ACQ_LCB_MEAN || kind > BARK_ACQ_MES) return fail(BARK_ERR_ARG, "%s: unknown kind %d", name, kind);
+    const bool lcb = kind == BARK_ACQ_LCB_MEAN || kind == BARK_ACQ_LCB_MIXTURE;
+    if (!lcb && !targets) return fail(BARK_ERR_ARG, "%s: kind %d needs targets", name, kind);
+    if (!lcb && (S < 1 || S > ACQ_MAX_TARGETS))
+        return fail(BARK_ERR_ARG, "%s: between 1 and %lld targets per forest (got %lld)", name, (long long)ACQ_MAX_TARGETS, (long long)S);
+    if (!std::isfinite(kappa)) return fail(BARK_ERR_ARG, "%s: kappa is not finite", name);
+    int var = 0, rc;
+    if ((rc = bark_acquisition_plan(info->max_bits, info->m, variant, &var, nullptr))) return rc;
+    FittedCall fc;
+    if ((rc = fc.open(name, ctx, packed, info, d, noise, scale, state, state_bytes, info_out, workspace, Bc, stream_))) return rc;
+    const FittedAreas a = fitted_areas(workspace, fc.R, fc.Bc, C, P, var == 1, true);
+    if (workspace_bytes < a.total) return fail(BARK_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, a.total);
+    const int R = fc.R, m = fc.m, W = (int)a.W;
+    const PosteriorState &st = fc.st;
+    if ((rc = fc.copy_info(st.info, info_out, (int)fc.B))) return rc;
+    for (int64_t c0 = 0; c0 < fc.B; c0 += fc.Bc) {
+        const int bc = (int)(fc.B - c0 < fc.Bc ? fc.B - c0 : fc.Bc);
+        bark_pack_info sub;
+        const char *packed_c = fc.chunk(c0, bc, sub);
+        const double *w = st.w + (size_t)c0 * R;
+        const double *Minv = st.Minv + (size_t)c0 * R * R;
+        if (P > 0) {
+            if ((rc = walk_one_hot(packed_c, &sub, pending, P, fc.d, W, a.pcodes, ctx->fault, fc.caller))) return rc;
+            rc = acq_condition_from(a.pcodes, W, (int)a.ppad, (int)P, Minv, a.Minv, R, noise + c0, scale + c0, m, bc, st.info + c0,
+                                    fc.caller);
+            if (rc) return rc;
+            Minv = a.Minv;
+        }
+        if (var == 1 && (rc = acq_pack(Minv, w, R, bc, a.tab, fc.caller))) return rc;
+        for (int64_t s0 = 0; s0 < C; s0 += ACQ_SLAB) {
+            const int64_t n = C - s0 < ACQ_SLAB ? C - s0 : ACQ_SLAB;
+            if ((rc = walk_one_hot(packed_c, &sub, cand + (size_t)s0 * fc.d, n, fc.d, W, a.ccodes, ctx->fault, fc.caller))) return rc;
+            rc = acq_scan(var, lcb ? BARK_ACQ_LCB_MEAN : kind, a.ccodes, W, (int)bark_leaf_npad(n), (int)n, w, Minv, a.tab, R, noise + c0,
+                          scale + c0, m, bc, kappa, lcb ? nullptr : targets + (size_t)c0 * S, lcb ? 0 : (int)S, c0 == 0, a.acc + s0,
+                          (size_t)C, fc.caller);
+            if (rc) return rc;
+        }
+        if ((rc = fc.fault_info(info_out + c0, bc))) return rc;
+    }
+    return acq_finish(a.acc, C, (int)fc.B, kappa, kind, skip_idx, (int)n_skip, acq_out, a.part, a.part_i, info_out, best_out, idx_out,
+                      fc.caller);
+}
+
+// The state conditioned in place on P more points, in the order given (acq_condition_kernel on the state's M^-1; w does not
+// change).  A fault of the walk marks the state's status too: its M^-1 has then been conditioned on a leaf that means nothing.
+int bark_leaf_posterior_condition_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, int64_t d, const double *noise,
+                                      const double *scale, const double *pending, int64_t P, void *state, size_t state_bytes,
+                                      int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc, void *stream_) {
+    static const char *name = "bark_leaf_posterior_condition_hip";
+    error_buffer()[0] = 0;
+    if (!info) return fail(BARK_ERR_ARG, "%s: null argument", name);
+    if (P < 0 || P > ACQ_MAX_PENDING)
+        return fail(BARK_ERR_ARG, "%s: at most %lld pending points (got %lld)", name, (long long)ACQ_MAX_PENDING, (long long)P);
+    if (P > 0 && !pending) return fail(BARK_ERR_ARG, "%s: null argument", name);
+    FittedCall fc;
+    int rc;
+    if ((rc = fc.open(name, ctx, packed, info, d, noise, scale, state, state_bytes, info_out, workspace, Bc, stream_))) return rc;
+    const FittedAreas a = fitted_areas(workspace, fc.R, fc.Bc, 0, P, false, false);
+    if (workspace_bytes < a.total) return fail(BARK_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, a.total);
+    const PosteriorState &st = fc.st;
+    for (int64_t c0 = 0; P > 0 && c0 < fc.B; c0 += fc.Bc) {
+        const int bc = (int)(fc.B - c0 < fc.Bc ? fc.B - c0 : fc.Bc);
+        bark_pack_info sub;
+        const char *packed_c = fc.chunk(c0, bc, sub);
+        if ((rc = walk_one_hot(packed_c, &sub, pending, P, fc.d, (int)a.W, a.pcodes, ctx->fault, fc.caller))) return rc;
+        rc = acq_condition(a.pcodes, (int)a.W, (int)a.ppad, (int)P, st.Minv + (size_t)c0 * fc.R * fc.R, fc.R, noise + c0, scale + c0, fc.m,
+                           bc, st.info + c0, fc.caller);
+        if (rc || (rc = fc.fault_info(st.info + c0, bc))) return rc;
+    }
+    return fc.copy_info(st.info, info_out, (int)fc.B);
 }
 
 // Predictive scores (include/bark_hip.h, kernels in scores.hip): the scan's sequence with the points in place of the

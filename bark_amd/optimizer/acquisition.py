@@ -84,9 +84,21 @@ def _target_matrix(targets, B: int, kind: str, train_y):
     return t
 
 
+def _fitted(posterior, domain=None):
+    """The `posterior=` argument of the functions below, checked: a `tree_kernels.LeafPosterior` (`fit_posterior`), whose
+    feature types are those of `domain` when one is given too."""
+    from ..tree_kernels.posterior import LeafPosterior
+
+    if not isinstance(posterior, LeafPosterior):
+        raise TypeError(f"posterior must be a LeafPosterior (tree_kernels.fit_posterior), got {type(posterior).__name__}")
+    if domain is not None and not np.array_equal(_feat_types_of(domain), posterior.feat_types):
+        raise ValueError("the domain's feature types are not those the posterior was fitted with")
+    return posterior
+
+
 def acquisition_scan(model, data, candidates, domain, kappa: float = 1.96, kind: str = "lcb_mean",
                      return_values: bool = False, chunk: int | None = None, variant: str = "auto", pending=None, skip=None,
-                     targets=None):
+                     targets=None, posterior=None):
     """-> (best_value, best_index[, acq (C,)]): the minimum over the candidates of the acquisition and its index (ties:
     the lowest index); with `return_values` also the acquisition of every candidate.
 
@@ -118,9 +130,16 @@ def acquisition_scan(model, data, candidates, domain, kappa: float = 1.96, kind:
     tensor) that keep their value in `acq` but never win the minimum; with every candidate skipped the result is
     (NaN, -1).  With both None the call is the unconditioned scan, exactly as before.
 
+    posterior: a `tree_kernels.LeafPosterior` (`fit_posterior(model, data, domain)`): the call is then its `scan` — the same
+    scan from the fitted state, without the walk of the training points and the factorisation, bit for bit the result of this
+    function at the `chunk` of the fit — and `model`, `data` and `domain` may be None.  Without it nothing changes.
+
     Torch candidates give device scalars (0-d tensors) and a device vector, numpy candidates a float, an int and a numpy
     vector.  ValueError for an invalid categorical value, LinAlgError for a forest whose leaf-space system is not positive
     definite; there is no CPU fallback (RuntimeError without a GPU)."""
+    if posterior is not None:
+        return _fitted(posterior, domain).scan(candidates, kappa=kappa, kind=kind, return_values=return_values, chunk=chunk,
+                                               variant=variant, pending=pending, skip=skip, targets=targets)
     if kind not in KINDS:
         raise ValueError(f"unknown kind {kind!r} (use 'lcb_mean', 'lcb_mixture', 'ei', 'pi' or 'mes')")
     if variant not in VARIANTS:
@@ -176,28 +195,31 @@ def acquisition_scan(model, data, candidates, domain, kappa: float = 1.96, kind:
 
 
 def propose_from_candidates(model, data, candidates, domain, kappa: float = 1.96, kind: str = "lcb_mean",
-                            chunk: int | None = None, variant: str = "auto", targets=None):
+                            chunk: int | None = None, variant: str = "auto", targets=None, posterior=None):
     """The candidate row that minimises the acquisition (`acquisition_scan`): what the reference's `propose` returns when
     its search space is the given candidate set, and a better stand-in than its single random candidate when no solver is
-    available.  `targets`: those of kind "ei" / "pi" / "mes".  Torch candidates give a device row (the index is not read
-    back), numpy candidates a numpy row."""
+    available.  `targets`: those of kind "ei" / "pi" / "mes"; `posterior`: as in `acquisition_scan`.  Torch candidates give a
+    device row (the index is not read back), numpy candidates a numpy row."""
     _, idx = acquisition_scan(model, data, candidates, domain, kappa=kappa, kind=kind, chunk=chunk, variant=variant,
-                              targets=targets)
+                              targets=targets, posterior=posterior)
     if _is_torch(candidates):
         return candidates.index_select(0, idx.to(candidates.device).reshape(1))[0]
     return np.asarray(candidates)[idx]
 
 
 def propose_batch_from_candidates(model, data, candidates, domain, q: int, kappa: float = 1.96, kind: str = "lcb_mean",
-                                  pending=None, chunk: int | None = None, variant: str = "auto", targets=None):
+                                  pending=None, chunk: int | None = None, variant: str = "auto", targets=None, posterior=None):
     """-> (rows (q, d), indices (q,)): q distinct candidate rows chosen greedily.  Pick k is the arg-min of the scan
     conditioned on `pending` followed by picks 0 .. k-1 (`acquisition_scan(pending=..., skip=...)`), with those picks
     excluded: a point that is being evaluated no longer attracts the next one, because its variance has collapsed.
     With kind="ei" that is a greedy expected-improvement batch under the kriging believer; `targets` are the same for every pick.
 
-    A plain loop of q scans with no state kept between the picks, so the cost is q times one scan.  Torch candidates
-    give device tensors (a pick is gathered with index_select; no index is read back), numpy candidates numpy arrays.
-    ValueError for q < 1, q > C or P + q - 1 > 64 (the scan's limit on pending points)."""
+    Without `posterior` a plain loop of q scans with no state kept between the picks, so the cost is q times one scan, and
+    pick k replays the P + k downdates before it.  With a `tree_kernels.LeafPosterior` (`model`, `data` and `domain` may be
+    None) a private copy of its state is conditioned once on `pending` and once on every pick (`LeafPosterior.condition_`),
+    and the scans pass only the picks to skip: nothing is refitted, one downdate per forest and pick, the same rows and indices.
+    Torch candidates give device tensors (a pick is gathered with index_select; no index is read back), numpy candidates
+    numpy arrays.  ValueError for q < 1, q > C or P + q - 1 > 64 (the scan's limit on pending points), on both routes."""
     C = len(candidates)
     q = int(q)
     P = 0 if pending is None else len(pending)
@@ -214,6 +236,22 @@ def propose_batch_from_candidates(model, data, candidates, domain, q: int, kappa
         candidates = np.asarray(candidates)
         pend = None if P == 0 else np.asarray(pending.cpu() if _is_torch(pending) else pending, dtype=np.float64)
     rows, picks = [], []
+    if posterior is not None:
+        post = _fitted(posterior, domain).condition(pend)  # a copy, also when there is nothing to condition on
+        for k in range(q):
+            skip = None if not picks else torch.stack(picks) if on_device else picks
+            _, idx = post.scan(candidates, kappa=kappa, kind=kind, chunk=chunk, variant=variant, skip=skip, targets=targets)
+            if on_device:
+                idx = idx.to(candidates.device)
+                rows.append(candidates.index_select(0, idx.reshape(1))[0])
+            else:
+                rows.append(candidates[idx])
+            picks.append(idx)
+            if k + 1 < q:
+                post.condition_(rows[-1].reshape(1, -1))
+        if on_device:
+            return torch.stack(rows), torch.stack(picks)
+        return np.stack(rows), np.asarray(picks, dtype=np.int64)
     for _ in range(q):
         if on_device:
             cur = pend if not rows else torch.cat(([] if pend is None else [pend]) + [torch.stack(rows)])
@@ -235,24 +273,27 @@ def propose_batch_from_candidates(model, data, candidates, domain, q: int, kappa
 
 
 def propose_mes_from_candidates(model, data, candidates, domain, num_samples: int = 100, generator=None,
-                                chunk: int | None = None, variant: str = "auto", pending=None, skip=None):
+                                chunk: int | None = None, variant: str = "auto", pending=None, skip=None, posterior=None):
     """The candidate row with the largest information gain about the minimum value: the workflow of the reference's
     `propose_fidelity_information_based` (information_based_fidelity.py:16-36) with a candidate set in place of its single x.
     `generate_fstar_samples` draws num_samples joint posterior samples per forest at the training inputs and keeps their
     minima, (B, num_samples) on the device; `acquisition_scan(kind="mes", targets=...)` scores every candidate against
     them and returns the arg-min of the negated gain.  generator: a torch.Generator, an int seed or None, as
-    `generate_fstar_samples` takes it.  Torch candidates give a device row (the index is not read back), numpy
-    candidates a numpy row."""
+    `generate_fstar_samples` takes it.  posterior: as in `acquisition_scan`, for the scan; the draws of the minimum do not
+    read a fitted state, so `model`, `data` and `domain` are still needed.  Torch candidates give a device row (the index is
+    not read back), numpy candidates a numpy row."""
     import torch
 
     from .thompson_sampling import generate_fstar_samples
 
+    if model is None or data is None:
+        raise ValueError("propose_mes_from_candidates draws the minima from model and data: pass them beside the posterior")
     train_x, train_y = data
     # torch inputs keep the minima on the device between the two calls
     site_x = train_x if _is_torch(train_x) else torch.as_tensor(np.asarray(train_x, dtype=np.float64), device=_lib.torch_device())
     fstar = generate_fstar_samples(model, (site_x, train_y), domain, num_samples=num_samples, generator=generator)
     _, idx = acquisition_scan(model, data, candidates, domain, kind="mes", targets=fstar, chunk=chunk, variant=variant,
-                              pending=pending, skip=skip)
+                              pending=pending, skip=skip, posterior=posterior)
     if _is_torch(candidates):
         return candidates.index_select(0, idx.to(candidates.device).reshape(1))[0]
     return np.asarray(candidates)[idx]

@@ -11,8 +11,9 @@ on the device from that table (csrc/domain.hip) and scored by `acquisition_scan`
 * a larger grid is searched from the best of `n_candidates` random candidates by coordinate-wise local search over the moves
   "one coordinate to another cell", all neighbours of all incumbents scored in one scan per sweep.
 
-Every scan rebuilds the leaf-space systems of the B forests; keeping them between the scans of one search is future work
-(DESIGN.md section 8)."""
+By default every scan rebuilds the leaf-space systems of the B forests.  `propose_from_domain(reuse_fit=True)` fits them once
+(`tree_kernels.fit_posterior`) and runs every scan of the enumeration or the search from that state; `posterior=` takes a
+state fitted by the caller (DESIGN.md section 8 has the measured difference)."""
 
 from __future__ import annotations
 
@@ -235,7 +236,7 @@ def local_search(acq, candidates, neighbours, n_candidates: int, round_size: int
 def propose_from_domain(model, data, bounds, feat_types, kappa: float = 1.96, kind: str = "lcb_mean", n_candidates: int = 2 ** 18,
                         round_size: int = 2 ** 18, starts: int = 8, max_sweeps: int = 32, exhaustive_limit: int = 2 ** 22,
                         mode: str = "cells", seed: int = 0, pending=None, targets=None, chunk=None, variant: str = "auto",
-                        return_info: bool = False):
+                        return_info: bool = False, posterior=None, reuse_fit: bool = False):
     """-> x (d,) numpy float64: the point of the domain `bounds` / `feat_types` that minimises the acquisition, the reference's
     `propose` without its solver.  model, data, kind, kappa, pending and targets mean what they mean to `acquisition_scan`,
     through which every evaluation goes.  With return_info: (x, info).
@@ -247,15 +248,21 @@ def propose_from_domain(model, data, bounds, feat_types, kappa: float = 1.96, ki
     neighbour (`domain_neighbours`; ties: the lowest slot) while that is strictly lower; x is the best incumbent (ties: the
     better start).  The result does not depend on `round_size`, and a seed gives the same x every time.
 
+    reuse_fit=True fits the leaf-space posterior once (`tree_kernels.fit_posterior(model, data, feat_types, chunk)`), conditions
+    it once on `pending`, and runs every scan from that state: the same x and the same value, bit for bit, without a
+    factorisation per scan.  posterior: a `LeafPosterior` of the caller's to start from instead (it is not modified); `model`
+    and `data` may then be None.  The default fits per scan, as before.
+
     info: "value" (the acquisition at x), "exhaustive", "grid" (cells of the grid, a Python int), "index" (x's row of the grid,
-    -1 after a search), "sweeps", "scans" (calls of `acquisition_scan`), "start_values" and "final_values" (one per incumbent,
-    `starts` of them unless the candidates hold fewer distinct rows; empty when exhaustive).
+    -1 after a search), "sweeps", "scans" (calls of `acquisition_scan`), "fits" (factorisations of the B leaf-space systems:
+    the number of scans by default, 1 with reuse_fit, 0 with `posterior`), "start_values" and "final_values" (one per
+    incumbent, `starts` of them unless the candidates hold fewer distinct rows; empty when exhaustive).
 
     ValueError when starts times the table's total exceeds the scan's 2^24 candidates, and for what `acquisition_scan` and
     `split_table` refuse.  No CPU fallback."""
     import torch
 
-    from .acquisition import acquisition_scan
+    from .acquisition import _fitted, acquisition_scan
 
     n_candidates, round_size, starts, max_sweeps = int(n_candidates), int(round_size), int(starts), int(max_sweeps)
     if round_size < 1 or round_size > MAX_NEIGHBOURS:
@@ -265,10 +272,22 @@ def propose_from_domain(model, data, bounds, feat_types, kappa: float = 1.96, ki
     if mode not in ("cells", "uniform"):
         raise ValueError(f"unknown mode {mode!r} (use 'cells' or 'uniform')")
     b, ft = check_bounds(bounds, feat_types)
-    table = split_table(model[0], b, ft)
+    if posterior is not None:
+        posterior = _fitted(posterior, ft)
+    table = split_table(model[0] if posterior is None else posterior.forest, b, ft)
     plan = domain_plan(table)
     dev = _DeviceTable(table, b, ft)
     scan = dict(kappa=kappa, kind=kind, chunk=chunk, variant=variant, pending=pending, targets=targets)
+    fits = None  # one per scan
+    if posterior is not None or reuse_fit:
+        from ..tree_kernels.posterior import fit_posterior
+
+        fits = 0 if posterior is not None else 1
+        if posterior is None:
+            posterior = fit_posterior(model, data, ft, chunk=chunk)
+        if pending is not None and len(pending):
+            posterior = posterior.condition(pending)  # once per search; the caller's state stays as it is
+        scan.update(pending=None, posterior=posterior)
 
     if plan["grid"] <= exhaustive_limit:
         grid = plan["grid"]
@@ -288,7 +307,7 @@ def propose_from_domain(model, data, bounds, feat_types, kappa: float = 1.96, ki
         if at < 0:
             raise RuntimeError("the acquisition is NaN on every cell of the grid")
         info = {"value": float(best), "exhaustive": True, "grid": grid, "index": at, "sweeps": 0, "scans": scans,
-                "start_values": np.empty(0), "final_values": np.empty(0)}
+                "fits": scans if fits is None else fits, "start_values": np.empty(0), "final_values": np.empty(0)}
         return (x, info) if return_info else x
 
     if starts * plan["neighbours"] > MAX_NEIGHBOURS:
@@ -296,5 +315,5 @@ def propose_from_domain(model, data, bounds, feat_types, kappa: float = 1.96, ki
     x, info = local_search(
         lambda rows: acquisition_scan(model, data, rows, ft, return_values=True, **scan)[2],
         lambda first, n: dev.candidates(n, mode, seed, 0, first), dev.neighbours, n_candidates, round_size, starts, max_sweeps)
-    info.update(exhaustive=False, grid=plan["grid"])
+    info.update(exhaustive=False, grid=plan["grid"], fits=info["scans"] if fits is None else fits)
     return (x, info) if return_info else x

@@ -1,0 +1,170 @@
+"""The fitted leaf-space posterior as an object: fit once on the device, scan it many times.
+
+Every call of `bark_amd.optimizer.acquisition_scan` packs the forests, walks the N training points, forms and factorises
+I + c Z'Z for every forest, solves for w and M^-1, scores the candidates and throws all of that away.  `fit_posterior` does
+the part that does not depend on the candidates (bark_leaf_posterior_fit_hip) and returns a `LeafPosterior` that owns the
+result; its `scan` is the same scan from that state (bark_acquisition_scan_fitted_hip) and `condition` is the step a greedy
+batch takes between two picks (bark_leaf_posterior_condition_hip).  include/bark_hip.h has the contract: a scan from the
+state returns the bits of the stateless scan that uses the `chunk` the state was fitted with.
+"""
+
+from __future__ import annotations
+
+import math
+
+import numpy as np
+
+from .. import _lib
+from ..fitting.mll import _feat_types_of, _fit_chunk, _forest3, _leaf_call, _leaf_inputs, _raise_on_info
+from ..forest import _is_torch, _points
+
+MAX_TREES, MAX_LEAVES = 64, 8192  # limits of the leaf-space posterior (include/bark_hip.h)
+MAX_PENDING = 64  # points per call of `condition`, and pending points of a scan
+
+
+def _align256(n: int) -> int:
+    return (n + 255) & ~255
+
+
+class LeafPosterior:
+    """M^-1 (B, R, R), w (B, R) and the sweep's status of B forest samples fitted to (train_x, train_y), in one device
+    buffer (`state`, `nbytes` bytes), with what a scan needs beside them: the packed forests on the device (`packed`), the
+    forest records on the host (`forest`, for `propose_from_domain`'s cell table), `noise` and `scale` (device, (B,)),
+    `feat_types`, and B, m, R, d, N.  `info` is the device int32 status per forest (a view of the state; all zero unless a
+    later `condition_` met an invalid categorical value), `train_y_min` the default target of kind "ei" / "pi", `chunk` the
+    forests per chunk it was fitted with.  Made by `fit_posterior`; there is no CPU fallback."""
+
+    def __init__(self, q, state, chunk):
+        self.packed, self.forest, self.feat_types = q.pf, q.nodes3, q.ft
+        self.noise, self.scale = q.noise_d, q.scale_d
+        self.B, self.m, self.R, self.d, self.N = q.B, q.m, q.R, q.d, q.N
+        self.state, self.chunk = state, chunk
+        self.train_y_min = float(q.yd.min())
+
+    @property
+    def nbytes(self) -> int:
+        return int(self.state.numel())
+
+    @property
+    def info(self):
+        import torch
+
+        at = _align256(8 * self.B * self.R * self.R) + _align256(8 * self.B * self.R)
+        return self.state[at:at + 4 * self.B].view(torch.int32)
+
+    def _copy(self) -> "LeafPosterior":
+        new = object.__new__(LeafPosterior)
+        new.__dict__.update(self.__dict__)
+        new.state = self.state.clone()
+        return new
+
+    def _call(self, fn, need, chunk, *args):
+        """Run an entry point that starts from the state: args stand between `scale` and `info_out`."""
+        import torch
+
+        info = torch.empty(self.B, dtype=torch.int32, device=self.state.device)
+        Bc = int(chunk) if chunk else _fit_chunk(self.B, need)
+        ws = _lib.workspace(need(Bc))
+        _lib.check(fn(_lib.ctx(), _lib.ptr(self.packed.packed), self.packed.info_ref, self.d, _lib.ptr(self.noise), _lib.ptr(self.scale),
+                      *args, _lib.ptr(info), _lib.ptr(ws), ws.numel(), Bc, _lib.stream_ptr()))
+        _raise_on_info(info, "leaf-space system")
+
+    def scan(self, candidates, kappa: float = 1.96, kind: str = "lcb_mean", return_values: bool = False, chunk: int | None = None,
+             variant: str = "auto", pending=None, skip=None, targets=None):
+        """What `acquisition_scan(model, data, candidates, domain, ...)` returns, by the same numpy / torch conventions and
+        with the same errors, from the state: nothing of size N is touched.  The state is not modified; pending points
+        condition a scratch copy of M^-1 inside the call.  Bit for bit the stateless result at the `chunk` of the fit; the
+        `chunk` given here only bounds this call's workspace."""
+        from ..optimizer.acquisition import KINDS, TARGET_KINDS, VARIANTS, _skip_indices, _target_matrix, acquisition_plan
+
+        if kind not in KINDS:
+            raise ValueError(f"unknown kind {kind!r} (use 'lcb_mean', 'lcb_mixture', 'ei', 'pi' or 'mes')")
+        if variant not in VARIANTS:
+            raise ValueError(f"unknown variant {variant!r} (use 'auto', 'lds' or 'global')")
+        kappa = float(kappa)
+        if not math.isfinite(kappa):
+            raise ValueError(f"kappa must be finite, got {kappa}")
+        if len(candidates) < 1:
+            raise ValueError("acquisition scan needs at least one candidate")
+        tgt = _target_matrix(targets, self.B, kind, np.array([self.train_y_min])) if kind in TARGET_KINDS else None
+
+        import torch
+
+        cand_d = _points(candidates, self.d)[0]
+        C, R, dev = int(cand_d.shape[0]), self.R, self.state.device
+        acquisition_plan(R, self.m, variant)  # refuses variant="lds" past the LDS limit before anything is allocated
+        pend_d = None if pending is None or len(pending) == 0 else _points(pending, self.d)[0]
+        P = 0 if pend_d is None else int(pend_d.shape[0])
+        if P > MAX_PENDING:
+            raise ValueError(f"acquisition scan supports at most {MAX_PENDING} pending points (got {P})")
+        skip_d = None if skip is None else _skip_indices(skip, C)
+        tgt_d = None if tgt is None else _lib.to_device(tgt, torch.float64)
+        acq = torch.empty(C, dtype=torch.float64, device=dev) if return_values else None
+        best = torch.empty((), dtype=torch.float64, device=dev)
+        idx = torch.empty((), dtype=torch.int64, device=dev)
+        lib = _lib.lib()
+        self._call(lib.bark_acquisition_scan_fitted_hip,
+                   lambda k: int(lib.bark_acquisition_scan_fitted_workspace_bytes(R, self.m, k, C, P, VARIANTS[variant])), chunk,
+                   _lib.ptr(self.state), self.nbytes, _lib.ptr(cand_d), C, _lib.ptr(pend_d), P, _lib.ptr(skip_d),
+                   0 if skip_d is None else int(skip_d.numel()), _lib.ptr(tgt_d), 0 if tgt_d is None else int(tgt_d.shape[1]), kappa,
+                   KINDS[kind], VARIANTS[variant], _lib.ptr(acq), _lib.ptr(best), _lib.ptr(idx))
+        if _is_torch(candidates):
+            return (best, idx, acq) if return_values else (best, idx)
+        out = (float(best.item()), int(idx.item()))
+        return (*out, acq.cpu().numpy()) if return_values else out
+
+    def condition_(self, points) -> "LeafPosterior":
+        """Condition the state in place on `points` (P <= 64, d), in the order given, as `acquisition_scan(pending=points)`
+        conditions its own M^-1: one rank-one downdate per point and forest, w unchanged.  A later `scan()` equals the
+        stateless scan with these pending points, bit for bit; conditioning twice equals once on the concatenation.  After a
+        ValueError for an invalid categorical value the state is marked failed (`info` = -1)."""
+        if points is None or len(points) == 0:
+            return self
+        pend_d = _points(points, self.d)[0]
+        P = int(pend_d.shape[0])
+        if P > MAX_PENDING:
+            raise ValueError(f"at most {MAX_PENDING} pending points per call (got {P})")
+        lib = _lib.lib()
+        self._call(lib.bark_leaf_posterior_condition_hip,
+                   lambda k: int(lib.bark_leaf_posterior_condition_workspace_bytes(self.R, self.m, k, P)), None,
+                   _lib.ptr(pend_d), P, _lib.ptr(self.state), self.nbytes)
+        return self
+
+    def condition(self, points) -> "LeafPosterior":
+        """A new LeafPosterior conditioned on `points` (`condition_`): it shares the forests and owns a copy of the state."""
+        return self._copy().condition_(points)
+
+
+def fit_posterior(model, data, domain, chunk: int | None = None) -> LeafPosterior:
+    """The leaf-space posterior of the forest samples `model` = (forest, noise, scale) given `data` = (train_x, train_y), fitted
+    on the device and kept there: what every `acquisition_scan` computes before it looks at a candidate.  `domain` may be
+    feat_types.  chunk: forests factorised at a time (default: as many as fit the memory budget); a scan from the result
+    equals `acquisition_scan(..., chunk=chunk)` bit for bit.
+
+    Limits and errors are those of `acquisition_scan`: at most 64 trees and 8192 leaves per forest, ValueError for an invalid
+    categorical value in train_x, LinAlgError for a forest whose leaf-space system is not positive definite, RuntimeError
+    without a GPU (no CPU fallback).  Device memory kept: `nbytes` = 8 B (R^2 + R) + 4 B rounded up to 256-byte areas, plus
+    the packed forests."""
+    forest, noise, scale = model
+    train_x, train_y = data
+    nodes3 = _forest3(forest)
+    m = int(nodes3.shape[1])
+    if m > MAX_TREES:
+        raise ValueError(f"a fitted posterior supports at most {MAX_TREES} trees (got {m})")
+    if scale is None:
+        raise ValueError("a fitted posterior needs scale")
+
+    import torch
+
+    q = _leaf_inputs(nodes3, noise, scale, train_x, train_y, _feat_types_of(domain))
+    if q.R > MAX_LEAVES:
+        raise ValueError(f"a fitted posterior supports at most {MAX_LEAVES} leaves per forest (got {q.R})")
+    lib = _lib.lib()
+    nbytes = int(lib.bark_leaf_posterior_bytes(q.R, q.pf.m, q.B))
+    if nbytes == 0:
+        raise ValueError(f"a fitted posterior refuses the shape B = {q.B}, m = {q.pf.m}, R = {q.R}")
+    state = torch.empty(nbytes, dtype=torch.uint8, device=q.device)
+    need = lambda k: int(lib.bark_leaf_posterior_fit_workspace_bytes(q.N, q.R, q.pf.m, k))  # noqa: E731
+    Bc = int(chunk) if chunk else _fit_chunk(q.B, need)
+    _leaf_call(q, lib.bark_leaf_posterior_fit_hip, need, Bc, _lib.ptr(state), nbytes)
+    return LeafPosterior(q, state, Bc)

@@ -453,6 +453,61 @@ int bark_acquisition_scan_targets_hip(bark_ctx *ctx, const void *packed, const b
                                       size_t workspace_bytes, int64_t Bc, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Fitted leaf-space posterior: fit once, then scan and condition from the state.  Every scan above starts from nothing: it
+ * walks the N training points, forms and factorises M = I_R + c Z'Z per forest, solves for w and M^-1, scores the candidates
+ * and drops all of it.  These entry points keep what the candidates are scored with, in a buffer the caller owns.
+ * state: device, 256-byte aligned, bark_leaf_posterior_bytes(R, m, B) bytes: M^-1 (B, R, R) fp64, w (B, R) fp64 and the
+ *   sweep's status per forest (B int32), each area rounded up to 256 bytes: align(8 B R^2) + align(8 B R) + align(4 B).  The
+ *   query returns 0 for a shape the scan refuses (m > 64, R > 8192, B < 1).  The state depends on (packed, X, y, noise,
+ *   scale) only; the calls that read it take packed / info / noise / scale again, for the candidate walk and the constants,
+ *   and they must be the ones it was fitted with.  No X, no y, nothing of size N after the fit.
+ * bark_leaf_posterior_fit_hip: per chunk of Bc forests exactly the opening sequence of bark_acquisition_scan_hip (leaf walk,
+ *   M, the R x R sweep with an identity right-hand side, w = V'z, M^-1 = V'V), with the two results written into the state in
+ *   place.  info_out[b] and the state's status: 0, k > 0 (pivot k of M_b not positive) or -1 (invalid categorical value in X).
+ *   A scan from the state therefore reads the bits the stateless scan with the same Bc computes (the sweep's schedule may
+ *   depend on Bc, hence "the same").  workspace >= bark_leaf_posterior_fit_workspace_bytes(N, R, m, Bc): the sweep's areas
+ *   and the codes of the N points; no candidate, scan or pending areas.
+ * bark_acquisition_scan_fitted_hip: bark_acquisition_scan_targets_hip from the state — all five kinds, pending, skip_idx,
+ *   targets, variant and every formula and summation order as documented above; acq_scan / acq_finish are the same kernels.
+ *   The state is not modified: with P > 0 the chunk's M^-1 is conditioned into a scratch area of the workspace, the first
+ *   downdate reading the state and writing the scratch, the others in place there, with the arithmetic and order of the
+ *   pending entry point.  Hence the result equals that of the stateless call with the Bc of the fit, bit for bit, and does
+ *   not depend on this call's Bc.  info_out[b]: the state's status, or -1 for an invalid categorical value in a candidate or
+ *   pending point of this call; any non-zero entry makes best_out / idx_out NaN / -1.
+ *   workspace >= bark_acquisition_scan_fitted_workspace_bytes(R, m, Bc, C, P, variant) (0 for a refused shape or variant):
+ *   the codes of at most 65536 candidates for Bc forests, Bc (R (R + 1) / 2 + R) doubles when the LDS variant runs,
+ *   3 C + C / 128 doubles, and with P > 0 the pending codes and Bc R^2 doubles of scratch.
+ * bark_leaf_posterior_condition_hip: the state conditioned in place on P more points, in the order given — the downdates
+ *   of the pending entry point applied to the state's M^-1 (w does not change).  Conditioning on P1 points and then on P2
+ *   is, bit for bit, conditioning on the P1 + P2 in that order, and a later plain scan equals the stateless scan with those
+ *   pending points.  This is the step between the picks of a greedy batch: one downdate per forest instead of a refit.
+ *   0 <= P <= 64 per call.  An invalid categorical value in a point sets info_out and the state's status to -1: that state's
+ *   M^-1 is no longer meaningful.  Forests whose status is non-zero are left alone.
+ *   workspace >= bark_leaf_posterior_condition_workspace_bytes(R, m, Bc, P): the pending codes.
+ * Limits, refused with BARK_ERR_ARG before any launch: those of bark_acquisition_scan_targets_hip; a state buffer smaller
+ * than bark_leaf_posterior_bytes or not 256-byte aligned.  The calls only enqueue; the queries are pure host code.
+ * ------------------------------------------------------------------------------------- */
+size_t bark_leaf_posterior_bytes(int64_t max_bits, int64_t m, int64_t B);
+size_t bark_leaf_posterior_fit_workspace_bytes(int64_t N, int64_t max_bits, int64_t m, int64_t Bc);
+int bark_leaf_posterior_fit_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N, int64_t d,
+                                const double *y, const double *noise, const double *scale, void *state, size_t state_bytes,
+                                int32_t *info_out /* (B,) */, void *workspace, size_t workspace_bytes, int64_t Bc, void *stream);
+size_t bark_acquisition_scan_fitted_workspace_bytes(int64_t max_bits, int64_t m, int64_t Bc, int64_t C, int64_t P, int variant);
+int bark_acquisition_scan_fitted_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, int64_t d, const double *noise,
+                                     const double *scale, const void *state, size_t state_bytes, const double *cand, int64_t C,
+                                     const double *pending /* (P, d) or NULL */, int64_t P,
+                                     const int64_t *skip_idx /* (n_skip,) or NULL */, int64_t n_skip,
+                                     const double *targets /* (B, S) or NULL for kinds 0 / 1 */, int64_t S, double kappa, int kind,
+                                     int variant, double *acq_out /* (C,) or NULL */, double *best_out /* 1 */,
+                                     int64_t *idx_out /* 1 */, int32_t *info_out /* (B,) */, void *workspace,
+                                     size_t workspace_bytes, int64_t Bc, void *stream);
+size_t bark_leaf_posterior_condition_workspace_bytes(int64_t max_bits, int64_t m, int64_t Bc, int64_t P);
+int bark_leaf_posterior_condition_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, int64_t d, const double *noise,
+                                      const double *scale, const double *pending /* (P, d) */, int64_t P, void *state,
+                                      size_t state_bytes, int32_t *info_out /* (B,) */, void *workspace, size_t workspace_bytes,
+                                      int64_t Bc, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Predictive scores: how well the forest samples predict targets y_c at C points, in the same leaf space and again without
  * (B, C) arrays — what the reference's bark.utils.metrics (gaussian_log_likelihood, nlpd, mse; metrics.py:5-39) gives when fed
  * forest_predict's output, per forest and for the equally weighted mixture of the forests.  With
