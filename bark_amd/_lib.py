@@ -164,6 +164,13 @@ SIGNATURES = {
     "bark_leaf_posterior_condition_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64]),
     "bark_leaf_posterior_condition_hip": (ci, [vp, vp, ctypes.POINTER(PackInfo), i64, vp, vp, vp, i64, vp, ctypes.c_size_t, vp, vp,
                                                ctypes.c_size_t, i64, vp]),
+    "bark_leaf_posterior_paths_plan": (ci, [i64, i64, ctypes.POINTER(ci), ctypes.POINTER(i64)]),
+    "bark_leaf_posterior_paths_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64, ci]),
+    "bark_leaf_posterior_paths_hip": (ci, [vp, ctypes.POINTER(PackInfo), vp, vp, vp, ctypes.c_size_t, vp, vp, i64, vp, ctypes.c_uint64,
+                                           vp, vp, vp, ctypes.c_size_t, vp]),
+    "bark_path_scan_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64, ci]),
+    "bark_path_scan_hip": (ci, [vp, vp, ctypes.POINTER(PackInfo), i64, vp, vp, i64, vp, i64, ci, vp, vp, vp, vp, vp, ctypes.c_size_t,
+                                vp]),
     "bark_predictive_scores_workspace_bytes":(ctypes.c_size_t, [i64, i64, i64, i64, i64]),
     "bark_predictive_scores_hip": (ci, [vp, vp, ctypes.POINTER(PackInfo), vp, i64, i64, vp, vp, vp, vp, i64, vp, ci, ci, vp, vp, vp,
                                         vp, vp, ctypes.c_size_t, i64, vp]),

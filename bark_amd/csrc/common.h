@@ -156,6 +156,10 @@ int sample_weights(const double *V, long ldv, long vstride, const double *w, con
 // doubles) and `part_i` (as many int64)
 int sample_gather(const uint32_t *ccodes, int W, int cpad, int C, const double *Wt, int Rpad, int Spad, int S, int m, int bc,
                   int reduce, double *f, double *red, int64_t *ridx, double *part, int64_t *part_i, hipStream_t s);
+// the reduction's second step alone (MAX or MIN): red / ridx (bc, S) from partials laid out part[b][k][s], k < nblk in
+// increasing candidate order; paths.hip feeds it the partials of its own scan
+int sample_finish(const double *part, const int64_t *part_i, int nblk, int S, int bc, int reduce, double *red, int64_t *ridx,
+                  hipStream_t s);
 
 // acquire.hip
 constexpr int ACQ_TILE = 256;               // points per workgroup of the scan and the score kernels, one per thread

@@ -214,6 +214,12 @@ int sample_gather(const uint32_t *ccodes, int W, int cpad, int C, const double *
                            (double *)nullptr, part, part_i);
     BARK_LAUNCH_CHECK();
     if (reduce == BARK_SAMPLE_FULL) return BARK_OK;
+    return sample_finish(part, part_i, nblk, S, bc, reduce, red, ridx, s);
+}
+
+// red / ridx (bc, S) from the partials part[b][k][s] of nblk workgroups, in increasing candidate order (MAX or MIN)
+int sample_finish(const double *part, const int64_t *part_i, int nblk, int S, int bc, int reduce, double *red, int64_t *ridx,
+                  hipStream_t s) {
     const unsigned fg = (unsigned)((bc * S + 255) / 256);
     if (reduce == BARK_SAMPLE_MAX)
         hipLaunchKernelGGL(sample_finish_kernel<1>, dim3(fg), dim3(256), 0, s, part, part_i, nblk, S, bc, red, ridx);

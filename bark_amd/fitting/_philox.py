@@ -37,3 +37,25 @@ def uniforms(seed: int, chain, tree, sweep: int, n_draws: int) -> np.ndarray:
     words = philox4x32((seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF), ctr).astype(np.uint64).reshape(chain.shape[0], blocks * 2, 2)
     x = words[..., 0] | (words[..., 1] << _S32)
     return ((x >> np.uint64(11)).astype(np.float64) * 2.0 ** -53)[:, :n_draws]
+
+
+PATH_KEY = 0x70617468  # "path": csrc/paths.hip xors it into the key's high word
+
+
+def path_normals(seed: int, forest, draw, R: int) -> np.ndarray:
+    """The standard normals of the sample paths (forest[i], draw[i]) -> (len(forest), R), as csrc/paths.hip draws them when
+    no eps is given: key = (seed low word, seed high word ^ PATH_KEY), counter = (forest, draw, a // 2, 0) for entry a; with
+    u1, u2 the block's two uniforms, r = sqrt(-2 log(1 - u1)) and th = 6.283185307179586 u2, the even entry is r cos th and
+    the odd one r sin th.  A row depends on (seed, forest, draw) only."""
+    forest = np.asarray(forest, dtype=np.uint64).reshape(-1)
+    draw = np.broadcast_to(np.asarray(draw, dtype=np.uint64).reshape(-1), forest.shape)
+    half = (int(R) + 1) // 2
+    ctr = np.zeros((forest.shape[0], half, 4), dtype=np.uint64)
+    ctr[..., 0], ctr[..., 1] = forest[:, None], draw[:, None]
+    ctr[..., 2] = np.arange(half, dtype=np.uint64)[None, :]
+    seed = int(seed) & (2 ** 64 - 1)
+    words = philox4x32((seed & 0xFFFFFFFF, ((seed >> 32) & 0xFFFFFFFF) ^ PATH_KEY), ctr).astype(np.uint64)
+    u1 = ((words[..., 0] | (words[..., 1] << _S32)) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+    u2 = ((words[..., 2] | (words[..., 3] << _S32)) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+    r, th = np.sqrt(-2.0 * np.log(1.0 - u1)), 6.283185307179586 * u2
+    return np.stack([r * np.cos(th), r * np.sin(th)], axis=-1).reshape(forest.shape[0], 2 * half)[:, :int(R)]

@@ -6,3 +6,5 @@ from .acquisition import (acquisition_plan, acquisition_scan, propose_batch_from
                           propose_from_candidates, propose_mes_from_candidates)
 from .domain import (CellTable, domain_candidates, domain_neighbours, domain_plan, propose_from_domain,  # noqa: F401
                      split_table)
+from .thompson_sampling import (propose_thompson_from_candidates, propose_thompson_from_domain,  # noqa: F401
+                                thompson_forests)

@@ -134,6 +134,49 @@ class LeafPosterior:
         """A new LeafPosterior conditioned on `points` (`condition_`): it shares the forests and owns a copy of the state."""
         return self._copy().condition_(points)
 
+    def sample_paths(self, num_samples: int = 1, *, forests=None, seed: int = 0, eps=None) -> LeafPaths:
+        """Posterior sample paths from the state (bark_leaf_posterior_paths_hip): for path (b, s) the leaf weights
+        W = c_b w_b + sqrt(scale_b / m) G_b eps, G_b the lower Cholesky factor of the state's M_b^-1 — of the conditioned matrix
+        after `condition`, so the paths then respect the pending points.
+
+        forests=None: `num_samples` paths of every forest, b-major (P = B num_samples).  forests=(P,) ints: one path per entry,
+        entry i with the draw number equal to the count of earlier entries naming the same forest; the result is in the caller's
+        order.  eps: (P, R) standard normals, numpy or torch, row i for path i; without it the normals are Philox draws named by
+        (`seed`, b, s) alone (fitting/_philox.path_normals restates them), so the same seed gives the same path whatever else is
+        asked for; torch's generator is not used.  Every forest that occurs is factorised once per 4096 paths.
+
+        A forest whose M^-1 is not positive definite (or whose status is non-zero) gives NaN paths; nothing is raised here.
+        ValueError for forests past `paths_plan`'s limit.  No CPU fallback."""
+        import ctypes
+
+        import torch
+
+        paths_plan(self.R, self.m)
+        if not isinstance(seed, (int, np.integer)):
+            raise TypeError(f"seed must be an int, got {type(seed).__name__}")
+        forest, draw, order = path_list(forests, self.B, num_samples)
+        P, R, dev = int(forest.shape[0]), self.R, self.state.device
+        eps_d = None
+        if eps is not None:
+            eps_d = _lib.to_device(eps.detach() if _is_torch(eps) else np.asarray(eps, dtype=np.float64), torch.float64)
+            if tuple(eps_d.shape) != (P, R):
+                raise ValueError(f"eps must be ({P}, {R}), got {tuple(eps_d.shape)}")
+            eps_d = eps_d[torch.from_numpy(order).to(dev)].contiguous()
+        sf, sd = np.ascontiguousarray(forest[order]), np.ascontiguousarray(draw[order])
+        W = torch.empty((P, R), dtype=torch.float64, device=dev)
+        info = torch.empty(self.B, dtype=torch.int32, device=dev)
+        lib = _lib.lib()
+        for p0 in range(0, P, MAX_PATHS_PER_CALL):
+            n = min(MAX_PATHS_PER_CALL, P - p0)
+            ws = _lib.workspace(int(lib.bark_leaf_posterior_paths_workspace_bytes(R, self.m, self.B, n, eps_d is None)))
+            _lib.check(lib.bark_leaf_posterior_paths_hip(
+                _lib.ctx(), self.packed.info_ref, _lib.ptr(self.noise), _lib.ptr(self.scale), _lib.ptr(self.state), self.nbytes,
+                _lib.ptr(sf[p0:p0 + n]), _lib.ptr(sd[p0:p0 + n]), n, _lib.ptr(None if eps_d is None else eps_d[p0:p0 + n]),
+                ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), _lib.ptr(W[p0:p0 + n]), _lib.ptr(info), _lib.ptr(ws), ws.numel(),
+                _lib.stream_ptr()))
+        return LeafPaths(self, W, forest, draw, order)
+
+
 
 def fit_posterior(model, data, domain, chunk: int | None = None) -> LeafPosterior:
     """The leaf-space posterior of the forest samples `model` = (forest, noise, scale) given `data` = (train_x, train_y), fitted
@@ -168,3 +211,121 @@ def fit_posterior(model, data, domain, chunk: int | None = None) -> LeafPosterio
     Bc = int(chunk) if chunk else _fit_chunk(q.B, need)
     _leaf_call(q, lib.bark_leaf_posterior_fit_hip, need, Bc, _lib.ptr(state), nbytes)
     return LeafPosterior(q, state, Bc)
+
+
+MAX_PATHS_PER_CALL = 4096  # paths per call of the two path entry points (include/bark_hip.h)
+
+
+def paths_plan(R: int, m: int) -> dict:
+    """{"route": the factorisation `sample_paths` takes for forests of R leaves and m trees ("blocked"), "max_leaves": its
+    limit}; ValueError for a shape it refuses (bark_leaf_posterior_paths_plan).  Host only."""
+    import ctypes
+
+    route, limit = ctypes.c_int(0), ctypes.c_int64(0)
+    _lib.check(_lib.lib().bark_leaf_posterior_paths_plan(int(R), int(m), ctypes.byref(route), ctypes.byref(limit)))
+    return {"route": {1: "blocked"}[route.value], "max_leaves": int(limit.value)}
+
+
+def path_list(forests, B: int, num_samples: int = 1):
+    """The (forest, draw) pairs `sample_paths` takes, host only -> (forest (P,), draw (P,), order (P,)), int32 / int32 / int64.
+    forests=None: num_samples paths of every forest, b-major.  Otherwise one path per entry, entry i taking the draw number
+    equal to the count of earlier entries that name the same forest.  `order` sorts the paths by forest, stably: the device
+    takes forest[order], and row j of its result is the caller's path order[j]."""
+    if forests is None:
+        S = int(num_samples)
+        if S < 1:
+            raise ValueError(f"num_samples must be positive, got {num_samples}")
+        forest = np.repeat(np.arange(B, dtype=np.int32), S)
+        return forest, np.tile(np.arange(S, dtype=np.int32), B), np.arange(B * S, dtype=np.int64)
+    f = np.asarray(forests)
+    if f.ndim != 1 or f.shape[0] < 1 or not np.issubdtype(f.dtype, np.integer):
+        raise ValueError("forests must be a non-empty 1-d array of ints")
+    if f.min() < 0 or f.max() >= B:
+        raise ValueError(f"forests must lie in [0, {B})")
+    forest = f.astype(np.int32)
+    order = np.argsort(forest, kind="stable").astype(np.int64)
+    srt = forest[order]
+    start = np.flatnonzero(np.r_[True, srt[1:] != srt[:-1]])
+    run = np.repeat(start, np.diff(np.r_[start, srt.shape[0]]))
+    draw = np.empty(forest.shape[0], dtype=np.int32)
+    draw[order] = np.arange(srt.shape[0]) - run  # stable sort: the rank inside a forest's run is the count of earlier entries
+    return forest, draw, order
+
+
+class LeafPaths:
+    """P posterior sample paths of a `LeafPosterior`: `forest` and `draw` (P,) name them, `W` (P, R, device, float64) holds
+    their leaf weights in the caller's order, and `posterior` gives the packed forests they are evaluated under.  A path is
+    the function f(x) = sum_t W[leaf_t(x)]; `evaluate` and `minimise` take any candidates, any number of times
+    (bark_path_scan_hip).  Made by `LeafPosterior.sample_paths`."""
+
+    def __init__(self, posterior, W_sorted, forest, draw, order):
+        import torch
+
+        self.posterior, self.forest, self.draw = posterior, forest, draw
+        self._W, self._order = W_sorted, order
+        self._sorted_forest = np.ascontiguousarray(forest[order])
+        self._inverse = torch.from_numpy(np.argsort(order)).to(W_sorted.device)
+        self.P = int(forest.shape[0])
+
+    @property
+    def W(self):
+        return self._W[self._inverse]
+
+    def subset(self, index) -> "LeafPaths":
+        """The paths `index` (ints into the caller's order) as a LeafPaths of their own: same posterior, a copy of their rows."""
+        import torch
+
+        index = np.asarray(index, dtype=np.int64).reshape(-1)
+        forest, draw = self.forest[index], self.draw[index]
+        order = np.argsort(forest, kind="stable").astype(np.int64)
+        rows = self._inverse[torch.from_numpy(index[order]).to(self._W.device)]
+        return LeafPaths(self.posterior, self._W[rows].contiguous(), forest, draw, order)
+
+    def _scan(self, candidates, reduce):
+        import torch
+
+        post = self.posterior
+        if len(candidates) < 1:
+            raise ValueError("a path scan needs at least one candidate")
+        cand_d = _points(candidates, post.d)[0]
+        C, P, dev = int(cand_d.shape[0]), self.P, self._W.device
+        full = reduce == _lib.SAMPLE_FULL
+        if full:
+            from .tree_gps import _check_output_budget
+
+            _check_output_budget(8 * P * C, f"evaluate: {P} paths at {C} candidates")
+        f = torch.empty((P, C), dtype=torch.float64, device=dev) if full else None
+        red = None if full else torch.empty(P, dtype=torch.float64, device=dev)
+        idx = None if full else torch.empty(P, dtype=torch.int64, device=dev)
+        info = torch.empty(post.B, dtype=torch.int32, device=dev)
+        lib = _lib.lib()
+        bad = np.zeros(post.B, dtype=bool)
+        for p0 in range(0, P, MAX_PATHS_PER_CALL):
+            n = min(MAX_PATHS_PER_CALL, P - p0)
+            need = int(lib.bark_path_scan_workspace_bytes(post.R, post.m, n, C, reduce))
+            if need == 0:
+                raise ValueError(f"a path scan refuses the shape R = {post.R}, m = {post.m}, P = {n}, C = {C}")
+            ws = _lib.workspace(need)
+            _lib.check(lib.bark_path_scan_hip(
+                _lib.ctx(), _lib.ptr(post.packed.packed), post.packed.info_ref, post.d, _lib.ptr(self._sorted_forest[p0:p0 + n]),
+                _lib.ptr(self._W[p0:p0 + n]), n, _lib.ptr(cand_d), C, reduce, _lib.ptr(None if f is None else f[p0:p0 + n]),
+                _lib.ptr(None if red is None else red[p0:p0 + n]), _lib.ptr(None if idx is None else idx[p0:p0 + n]),
+                _lib.ptr(info), _lib.ptr(ws), ws.numel(), _lib.stream_ptr()))
+            bad |= info.cpu().numpy() != 0
+        _raise_on_info(np.where(bad, -1, 0), "leaf-space system")
+        inv = self._inverse
+        return (f[inv],) if full else (red[inv], idx[inv])
+
+    def evaluate(self, candidates):
+        """-> (P, C) float64: every path at every candidate, the trees summed in the order t = 0..m-1 (bit for bit a host
+        loop over the leaf weights).  numpy candidates give numpy, torch candidates a device tensor.  A path of a forest
+        whose state is not positive definite is a NaN row.  Errors: those of `LeafPosterior.scan`; ValueError when the
+        output exceeds the memory budget."""
+        (f,) = self._scan(candidates, _lib.SAMPLE_FULL)
+        return f if _is_torch(candidates) else f.cpu().numpy()
+
+    def minimise(self, candidates, maximise: bool = False):
+        """-> (values (P,), indices (P,) int64): each path's minimum (maximum) over the candidates, the bits `evaluate` gives,
+        and its index, the lowest among equals; NaN and -1 for a NaN path.  No (P, C) array is formed."""
+        red, idx = self._scan(candidates, _lib.SAMPLE_MAX if maximise else _lib.SAMPLE_MIN)
+        return (red, idx) if _is_torch(candidates) else (red.cpu().numpy(), idx.cpu().numpy())

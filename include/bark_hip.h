@@ -508,6 +508,63 @@ int bark_leaf_posterior_condition_hip(bark_ctx *ctx, const void *packed, const b
                                       int64_t Bc, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Sample paths from a fitted posterior (Thompson sampling).  A tree kernel has finite rank, so a posterior draw of forest b
+ * is exactly a table of R leaf weights, W ~ N(c_b w_b, (scale_b / m) M_b^-1), and the sample path is the function
+ * f(x) = sum_t W[col_t(x)]: once the table exists it is evaluated anywhere, later, with m gathers per point.
+ * A path is a pair (forest b, draw number s).  The path list is given as two HOST arrays, path_forest (P,) int32,
+ * non-decreasing, entries in [0, B), and path_draw (P,) int32 >= 0; both are read before the call returns.  A forest that
+ * does not occur costs nothing: it is neither factorised nor walked.
+ * bark_leaf_posterior_paths_hip: for path p with b = path_forest[p], s = path_draw[p]
+ *     W_out[p, :] = c_b w_b + sqrt(scale_b / m) G_b eps[p, :]          c_b = scale_b / (m s2_b) as everywhere above
+ *   with G_b the lower Cholesky factor (positive diagonal, hence unique) of the state's M_b^-1 — after
+ *   bark_leaf_posterior_condition_hip the conditioned matrix, so paths of a conditioned state respect the pending points.
+ *   Every forest that occurs is factorised once per call.  Row a of the product is sum_{k <= a} G[a][k] eps[p][k].
+ *   eps: (P, R) device, row p the standard normals of path p; or NULL: entry a of path (b, s) is then Box-Muller on
+ *   Philox4x32-10 with key = (seed low word, seed high word ^ 0x70617468 "path") and counter = (b, s, a / 2, 0): with
+ *   u1, u2 the block's two 64-bit draws (words (0, 1) and (2, 3), u = (x >> 11) 2^-53), r = sqrt(-2 log(1 - u1)) and
+ *   th = 6.283185307179586 u2, the even entry is r cos th and the odd one r sin th.  A path is therefore a function of
+ *   (seed, b, s) and the state only: not of P, of the other paths, of any chunking or of a launch shape.
+ *   info_out[b]: the state's status; or k > 0 when pivot k (1-based) of the factorisation of M_b^-1 is not positive.  The rows
+ *   of a forest with a non-zero info_out are NaN.  state / noise / scale / info as for the calls above (no packed forests).
+ *   Route: bark_leaf_posterior_paths_plan(R, m, &route, &max_leaves), pure host code, answers which factorisation a shape
+ *   takes and its limit.  There is one route, BARK_PATHS_ROUTE_BLOCKED: one workgroup per forest, left-looking over column
+ *   panels of 32, the 32 x 32 tiles through LDS and the factor in the workspace; it takes R <= 2048 (one CU does R^3 / 3
+ *   flops) and m <= 64.  Anything else is BARK_ERR_ARG from the plan and from the call, before any launch; never rerouted.
+ *   workspace >= bark_leaf_posterior_paths_workspace_bytes(R, m, B, P, eps == NULL): the run table, min(P, B, 256 MiB / 8 R^2)
+ *   factors of R^2 doubles (more forests are factorised in rounds) and, without eps, the P R normals.
+ * bark_path_scan_hip: W (P, R) device — rows as W_out above, any values — evaluated at cand (C, d) device:
+ *     f[p, x] = sum_{t = 0 .. m-1} W[p][col_t^{b(p)}(x)]
+ *   the trees summed strictly in the order t = 0 .. m-1 starting from 0.0 (the order of bark_posterior_samples_hip), so the
+ *   value depends on no launch shape and a host loop reproduces it bit for bit.  reduce = BARK_SAMPLE_FULL: f_out (P, C).
+ *   BARK_SAMPLE_MAX / MIN: red_out (P,) the extreme over the candidates of those same bits and idx_out (P,) int64 its index
+ *   (ties: the lowest); fixed-order partials per workgroup of 256 candidates, then the finish kernel of
+ *   bark_posterior_samples_hip; no floating-point atomics.  Candidates are walked in slabs of at most 65536, only under the
+ *   forests that occur, at most 16 consecutive forests per walk.  info_out[b]: 0, or -1 when a walk that covered forest b met
+ *   an invalid categorical value (the forests walked together share the flag); the results of such a forest's paths are NaN
+ *   / -1.  A path whose value is NaN (a NaN row of W) has idx_out = -1.
+ *   workspace >= bark_path_scan_workspace_bytes(R, m, P, C, reduce): the run table, the codes of one slab for the forests of
+ *   one walk, and for MAX / MIN 16 bytes per (path, 256 candidates).
+ * Limits, refused with BARK_ERR_ARG before any launch: 1 <= P <= 4096 per call, 1 <= C <= 2^24, the plan's, a path list that
+ * is not non-decreasing or names a forest outside [0, B), a negative draw number, a short or misaligned state.  The byte
+ * queries return 0 for a refused shape and are pure host code.  The calls only enqueue, after copying the run table through
+ * the context's staging page (which waits for an earlier staged copy of the same context, nothing else).
+ * ------------------------------------------------------------------------------------- */
+#define BARK_PATHS_ROUTE_BLOCKED 1
+int bark_leaf_posterior_paths_plan(int64_t max_bits, int64_t m, int *route_out, int64_t *max_leaves_out);
+size_t bark_leaf_posterior_paths_workspace_bytes(int64_t max_bits, int64_t m, int64_t B, int64_t P, int normals);
+int bark_leaf_posterior_paths_hip(bark_ctx *ctx, const bark_pack_info *info, const double *noise, const double *scale,
+                                  const void *state, size_t state_bytes, const int32_t *path_forest /* host (P,) */,
+                                  const int32_t *path_draw /* host (P,) */, int64_t P, const double *eps /* (P, R) or NULL */,
+                                  uint64_t seed, double *W_out /* (P, R) */, int32_t *info_out /* (B,) */, void *workspace,
+                                  size_t workspace_bytes, void *stream);
+size_t bark_path_scan_workspace_bytes(int64_t max_bits, int64_t m, int64_t P, int64_t C, int reduce);
+int bark_path_scan_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, int64_t d,
+                       const int32_t *path_forest /* host (P,) */, const double *W /* (P, R) */, int64_t P, const double *cand,
+                       int64_t C, int reduce, double *f_out /* (P, C) or NULL */, double *red_out /* (P,) */,
+                       int64_t *idx_out /* (P,) */, int32_t *info_out /* (B,) */, void *workspace, size_t workspace_bytes,
+                       void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Predictive scores: how well the forest samples predict targets y_c at C points, in the same leaf space and again without
  * (B, C) arrays — what the reference's bark.utils.metrics (gaussian_log_likelihood, nlpd, mse; metrics.py:5-39) gives when fed
  * forest_predict's output, per forest and for the equally weighted mixture of the forests.  With
