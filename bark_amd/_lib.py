@@ -122,6 +122,7 @@ SIGNATURES = {
     "bark_tree_proposals_commit_hip": (ci, [vp, vp, vp, vp, i64, i64, i64, i64, vp]),
     "bark_domain_candidates_hip": (ci, [vp, vp, i64, vp, vp, i64, ci, ctypes.c_uint64, i64, i64, i64, vp, vp]),
     "bark_domain_neighbours_hip": (ci, [vp, vp, i64, i64, vp, i64, vp, vp]),
+    "bark_domain_repair_hip": (ci, [vp, vp, vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, i64, ci, vp, i64, vp, vp]),
     "bark_noise_scale_step_chains_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64]),
     "bark_noise_scale_step_chains_hip": (ci, [vp, vp, i64, i64, vp, ctypes.POINTER(PackInfo), vp, i64, vp, vp, vp, vp, vp, vp,
                                               vp, vp, ctypes.c_size_t, vp]),

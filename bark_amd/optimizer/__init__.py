@@ -4,7 +4,8 @@ the search over the whole domain that stands in for the reference's solver-based
 
 from .acquisition import (acquisition_plan, acquisition_scan, propose_batch_from_candidates,  # noqa: F401
                           propose_from_candidates, propose_mes_from_candidates)
-from .domain import (CellTable, domain_candidates, domain_neighbours, domain_plan, propose_from_domain,  # noqa: F401
-                     split_table)
+from .constraints import LinearConstraints  # noqa: F401
+from .domain import (CellBoxes, CellTable, cell_boxes, domain_candidates, domain_neighbours, domain_plan,  # noqa: F401
+                     domain_repair, propose_from_domain, split_table)
 from .thompson_sampling import (propose_thompson_from_candidates, propose_thompson_from_domain,  # noqa: F401
                                 thompson_forests)

@@ -886,7 +886,45 @@ int bark_domain_candidates_hip(const int64_t *cell_off, const double *cell_rep, 
 int bark_domain_neighbours_hip(const int64_t *cell_off, const double *cell_rep, int64_t total, int64_t d, const double *x, int64_t K,
                                double *out, void *stream);
 
-/* quick_inverse.py:37-38  mll(K_inv, K_logdet, y) = 0.5 * (-y' K_inv y - K_logdet), on device. */
+/* ---------------------------------------------------------------------------------------
+ * Domain repair — the reference's `propose` under the domain's linear input constraints (opt_core.py:90-99,
+ * bofire_mixed/constraints.py:122-133, proposals.py:56-66,150-202: "the feasible point closest to the centre" of a cell), as one
+ * step between "write rows" and "scan rows".  A cell is a box and moving a row inside its cell does not change one bit of its
+ * acquisition value, so every row is moved inside its own cell to a point with A x <= b (or = b), or marked infeasible.
+ *   The table: cell_off (d + 1) int64 as above, cell_lo / cell_hi (total) fp64 the USABLE closed interval of every cell (built by
+ *   bark_amd/optimizer/domain.py `cell_boxes`: a continuous cell (a, b] that is not its feature's first starts at nextafter(a)),
+ *   ascending and disjoint per feature; feat_types (d) int64.
+ *   The constraints, CSR: row_ptr (K + 1) int64 rising from 0, col (nnz) int64 ascending per row, coef (nnz) fp64; row k means
+ *   sum_f A_kf x_f <= b[k], or = b[k] where equality[k] != 0; tol (K) fp64 is the absolute slack of the final test.
+ * Per row of rows (n, d) fp64, in place; a feature is TOUCHED when some row of A stores a coefficient for it:
+ *   1. cell lookup: for every touched f, c = the first cell with x_f <= cell_hi[c] (binary search).  No such cell, x_f < cell_lo[c]
+ *      or a NaN x_f: feasible_out = 0 and the row is left as it was.  Untouched features are neither read nor written.
+ *   2. `passes` times, for k = 0 .. K - 1:  r = (sum_f A_kf x_f) - b_k, the sum from 0.0 over the row's stored coefficients in
+ *      order, multiply and add rounded separately (no FMA).  While r > 0 (equality: r != 0), walk the row's coefficients in order:
+ *      continuous x_f <- clamp(x_f - r / A_kf, lo_c, hi_c); integer (inequality rows only) x_f <- clamp(x_f - sign(A_kf)
+ *      ceil(r / |A_kf|), lo_c, hi_c); r is recomputed by the full sum after every change.  A zero coefficient, and an integer
+ *      feature of an equality row, moves nothing.
+ *   3. feasible_out = AND_k (r_k <= tol_k), |r_k| <= tol_k for equality rows, r_k recomputed once more.  An infeasible row
+ *      keeps what the passes left in it.
+ * Sound, always: a row marked feasible satisfies every constraint within tol and lies in its original cell — its leaf codes, and
+ *   so its acquisition value, are unchanged bit for bit.
+ * Complete when the rows of A have pairwise disjoint supports (K = 1 included): a row is marked feasible whenever its cell passes
+ *   the closed box test sum_f min(A_kf lo, A_kf hi) <= b_k (equality: min <= b_k <= max), up to the rounding that tol absorbs.
+ * A heuristic when supports overlap: a later constraint can undo an earlier one, feasible cells can be missed; an infeasible
+ *   point is never marked feasible.  No LP is built.
+ * Limits (refused before any launch): 1 <= d <= 4096, d <= total <= 2^20, 0 <= n <= 2^32, 1 <= K <= 16, 1 <= passes <= 64, a
+ * null pointer (rows and feasible_out may be NULL when n == 0, which launches nothing).  The constraint arrays are DEVICE memory
+ * and cannot be read before the launch: the kernel marks EVERY row infeasible, and writes nothing else, when row_ptr does not
+ * rise from 0 to at most 1024, a column lies outside 0 .. d - 1, more than 64 features are touched, or a touched feature's slice
+ * of the table lies outside 0 .. total.  One launch, no allocation, no synchronisation: capturable.
+ * ------------------------------------------------------------------------------------- */
+int bark_domain_repair_hip(const int64_t *cell_off, const double *cell_lo, const double *cell_hi, int64_t total,
+                           const int64_t *feat_types, int64_t d, const int64_t *row_ptr /* (K + 1) */,
+                           const int64_t *col /* nnz, ascending per row */, const double *coef /* nnz */, const double *b,
+                           const double *tol, const uint8_t *equality, int64_t K, int passes, double *rows /* (n, d) in/out */,
+                           int64_t n, uint8_t *feasible_out /* (n) */, void *stream);
+
+/* quick_inverse.py:37-38 mll(K_inv, K_logdet, y) = 0.5 * (-y' K_inv y - K_logdet), on device. */
 int bark_quadform_hip(const double *K_inv, const double *y, int64_t N, double *out, void *stream);
 /* out[b] = alpha * sum_i A[b * lda + i] * y[i] + beta * c[b] for b < B (c may be NULL) — e.g. log|K_s| =
  * -(y' K_s^-1 y) - 2 mll from the rows K_s^-1 y of the inverse export (opt_model.py:101) and the MLL vector. */

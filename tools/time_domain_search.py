@@ -4,6 +4,9 @@ candidates in the box, as many as the search scores, through acquisition_scan (D
   exhaustive   a small problem whose cell grid is enumerated: the exact minimiser
   search       B = 64, m = 50, N = 512, d = 10: multi-start local search from `cells` candidates
   random       the same problem, C uniform candidates in the box in one scan, C = the rows the search scored
+  search, budget   the same problem under one linear constraint (the six continuous features sum to at most 2.5): the search
+               with constraints=, the repair kernel alone on 2^18 rows, and uniform candidates filtered by hand, as many as
+               the search repaired (at most 2^21)
   fit / scan / batch   on the search problem: tree_kernels.fit_posterior alone, one LeafPosterior.scan of 2^18 candidates beside
                the stateless acquisition_scan, and a greedy batch of q = 8 over them with and without posterior=
 
@@ -81,6 +84,31 @@ def main():
     for C in (2 ** 18, min(scored, 2 ** 24)):
         ms, value = measure(lambda: random_route(C))
         print(json.dumps({"route": "random", "C": C, "value": value, "ms": round(ms, 2)}), flush=True)
+
+    # the search under one budget inequality over the continuous features: sum of the six <= 2.5
+    from bark_amd.optimizer import LinearConstraints, cell_boxes, domain_candidates, domain_repair
+
+    budget = LinearConstraints((ft == syn.CONT).astype(np.float64)[None], [2.5])
+    ms, (x, info) = measure(lambda: propose_from_domain(model, data, bounds, ft, seed=5, return_info=True, constraints=budget))
+    print(json.dumps({"route": "search, budget", "value": info["value"], "best_start": float(info["start_values"][0]),
+                      "sweeps": info["sweeps"], "scans": info["scans"], "rows_repaired": info["rows"], "feasible": info["feasible"],
+                      "budget_at_x": float(x[ft == syn.CONT].sum()), "ms": round(ms, 2)}), flush=True)
+    boxes, table = cell_boxes(F, bounds, ft), split_table(F, bounds, ft)
+    cells = domain_candidates(table, bounds, ft, 2 ** 18, "cells", 5)
+    ms, (_, ok) = measure(lambda: domain_repair(boxes, ft, budget, cells))  # with the copy that spares the caller's rows
+    print(json.dumps({"route": "repair", "rows": 2 ** 18, "touched": 6, "feasible": int(ok.sum()), "ms": round(ms, 3)}), flush=True)
+    cont = torch.as_tensor(ft == syn.CONT, device="cuda")
+
+    def filtered_route(C):
+        gen = torch.Generator(device="cuda").manual_seed(5)
+        cand = lo + torch.rand((6 * C, 10), dtype=torch.float64, device="cuda", generator=gen) * (hi - lo)
+        cand = torch.where(discrete, cand.floor(), cand)
+        cand = cand[cand[:, cont].sum(dim=1) <= 2.5][:C]  # what a user did by hand: keep the uniform candidates that comply
+        value, _ = acquisition_scan(model, data, cand, ft)
+        return float(value), int(cand.shape[0])
+
+    ms, (value, kept) = measure(lambda: filtered_route(min(info["rows"], 2 ** 21)))
+    print(json.dumps({"route": "random, filtered by hand", "C": kept, "value": value, "ms": round(ms, 2)}), flush=True)
 
     # the fitted state on the search problem: the fit alone, one scan from it, a greedy batch with and without it
     gen = torch.Generator(device="cuda").manual_seed(6)
