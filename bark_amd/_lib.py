@@ -25,6 +25,7 @@ MLL_INCLUDE_SCALE, MLL_INCLUDE_2PI, MLL_RHS_IDENTITY = 1, 2, 4
 SAMPLE_FULL, SAMPLE_MAX, SAMPLE_MIN = 0, 1, 2  # BARK_SAMPLE_*
 ACQ_LCB_MEAN, ACQ_LCB_MIXTURE, ACQ_EI, ACQ_PI, ACQ_MES = 0, 1, 2, 3, 4  # BARK_ACQ_*
 SCORE_HELDOUT, SCORE_LOO = 0, 1  # BARK_SCORE_*
+OBSERVE_VALUES, OBSERVE_SAMPLE = 0, 1  # BARK_OBSERVE_*
 DOMAIN_UNIFORM, DOMAIN_CELLS, DOMAIN_GRID = 0, 1, 2  # BARK_DOMAIN_*
 
 i64, vp, ci = ctypes.c_int64, ctypes.c_void_p, ctypes.c_int
@@ -165,6 +166,9 @@ SIGNATURES = {
     "bark_leaf_posterior_condition_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64]),
     "bark_leaf_posterior_condition_hip": (ci, [vp, vp, ctypes.POINTER(PackInfo), i64, vp, vp, vp, i64, vp, ctypes.c_size_t, vp, vp,
                                                ctypes.c_size_t, i64, vp]),
+    "bark_leaf_posterior_observe_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64]),
+    "bark_leaf_posterior_observe_hip": (ci, [vp, vp, ctypes.POINTER(PackInfo), i64, vp, vp, vp, i64, vp, i64, ci, vp, ctypes.c_uint64,
+                                             i64, vp, ctypes.c_size_t, vp, vp, vp, vp, ctypes.c_size_t, i64, vp]),
     "bark_leaf_posterior_paths_plan": (ci, [i64, i64, ctypes.POINTER(ci), ctypes.POINTER(i64)]),
     "bark_leaf_posterior_paths_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64, ci]),
     "bark_leaf_posterior_paths_hip": (ci, [vp, ctypes.POINTER(PackInfo), vp, vp, vp, ctypes.c_size_t, vp, vp, i64, vp, ctypes.c_uint64,

@@ -8,6 +8,7 @@
 // Only the upper triangle of M^-1 is read, m (m + 1) / 2 entries instead of leaf_predict_kernel's m^2.  The kernels:
 //   acq_condition_kernel  optional: M^-1 conditioned on the pending points (rank-one downdates), before anything reads it
 //   acq_condition_from_kernel  the same out of place, for the scan from a fitted state (the state is only read)
+//   acq_observe_kernel    a fitted state's M^-1 and w conditioned in place on points with observed or fantasised values
 //   acq_pack_kernel     upper triangle of M^-1, rows packed, followed by w: the image acq_scan_kernel stages in LDS
 //   acq_scan_kernel     one thread per candidate; the forests of the chunk in order, three running sums per candidate in
 //                       registers (sum of mu - kappa sd, of mu, of var + mu^2), kept in a (3, C) buffer between chunks
@@ -18,11 +19,13 @@
 // The order of every sum is fixed (leaves in code-bit order, targets 0 .. S-1, forests 0 .. B-1), so the result depends neither on the chunk
 // nor on the variant: the LDS and the global variant of acq_scan_kernel run the same arithmetic on the same values.
 #include "acq_point.h"
+#include "philox.h"
 
 namespace bark {
 namespace {
 
 constexpr int ACQ_COND_THREADS = 1024;         // acq_condition_kernel: one workgroup per forest
+constexpr uint32_t OBSERVE_KEY = 0x66616E74u;  // "fant": keeps the fantasies apart from every other stream of the same seed
 
 // Image (bc, tri + R): row a of the upper triangle of M^-1 at a (2R - a - 1) / 2 + a, i.e. entry (a, b >= a) at
 // a (2R - a - 1) / 2 + b; then w.
@@ -162,6 +165,117 @@ __global__ __launch_bounds__(ACQ_COND_THREADS) void acq_condition_from_kernel(co
         }
         __syncthreads();  // the next point reads the updated matrix and reuses t and the leaf list
     }
+}
+
+// Conditioning on P points with values: the state's M^-1 AND w, in place (include/bark_hip.h, bark_leaf_posterior_observe_hip).
+// Per point, in the order given, with t, q, g and the rewrite of M^-1 exactly as in acq_condition_kernel (the same products
+// and sums in the same order, so M^-1 ends with the bits that kernel leaves), and on top of them, by lane 0 of wave 0 in the
+// phase of the butterfly:
+//     s = sum_k w[a_k]  (k in code-bit order from 0.0: acq_scan_kernel's order),   mu = c s,   v = (scale / m) q + s2
+//     y* = values[b value_stride + p]   or   mu + sqrt(v) eps,   eps = eps[b P + p] or a Philox normal (below)
+//     logpred += -1/2 ( log v + (y* - mu)^2 / v ),     d = (y* - mu) / (1 + c q)
+// and by the whole workgroup, in the phase that rewrites M^-1:  w[i] += t[i] d.
+// Hand-overs: s is read from w between the barrier that publishes t and the one that publishes q and d, i.e. before this
+// point's rewrite of w and after the barrier that closes the previous point's; w and M^-1 are rewritten from t (LDS), which
+// nobody writes in that phase.  Every hand-over is a workgroup barrier, as in acq_condition_kernel, and nothing crosses
+// workgroups.  The Philox normal of (forest, draw, p): key (k0, k1) = (seed low word, seed high word ^ "fant"), counter
+// (b0 + b, draw, p / 2, 0), Box-Muller as paths_normals_kernel (paths.hip): even p takes r cos th, odd p takes r sin th.
+// Forests whose sweep failed (info != 0) are left alone; their rows of values_out / logpred_out are NaN.
+// LDS (8-byte items only): t [R], q, s, d, logpred, then the point's leaf list [ACQ_MAX_TREES] and its length.
+__global__ __launch_bounds__(ACQ_COND_THREADS) void acq_observe_kernel(const uint32_t *__restrict__ pcodes, int W, int ppad, int P,
+                                                                       double *Minv, double *wvec, int R,
+                                                                       const double *__restrict__ noise,
+                                                                       const double *__restrict__ scale, int m,
+                                                                       const int32_t *__restrict__ info, int mode,
+                                                                       const double *__restrict__ values, int value_stride,
+                                                                       const double *__restrict__ eps, uint32_t k0, uint32_t k1,
+                                                                       uint32_t b0, uint32_t draw, double *__restrict__ values_out,
+                                                                       double *__restrict__ logpred_out) {
+    extern __shared__ __attribute__((aligned(16))) double smem[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, b = blockIdx.x;
+    if (info[b] != 0) {  // the whole workgroup: no barrier is left waiting
+        if (values_out)
+            for (int p = tid; p < P; p += ACQ_COND_THREADS) values_out[(size_t)b * P + p] = NAN;
+        if (logpred_out && tid == 0) logpred_out[b] = NAN;
+        return;
+    }
+    double *t = smem;
+    double *qs = smem + R;
+    double *obs = smem + R + 1;  // s, d, logpred
+    int *leaves = reinterpret_cast<int *>(smem + R + 4);
+    int *count = leaves + ACQ_MAX_TREES;
+    double *Mb = Minv + (size_t)b * R * R;
+    double *wb = wvec + (size_t)b * R;
+    const double s2 = 1e-6 + noise[b];
+    const double c = scale[b] / ((double)m * s2);
+    if (tid == 0) obs[2] = 0.0;  // read and written by this thread only
+    for (int p = 0; p < P; ++p) {
+        if (tid == 0) {
+            int cnt = 0;
+            for (int w0 = 0; w0 < W; ++w0) {
+                uint32_t bits = pcodes[((size_t)b * W + w0) * ppad + p];
+                while (bits) {  // bits in increasing order: tree order
+                    const int a = 32 * w0 + __builtin_ctz(bits);
+                    if (cnt < ACQ_MAX_TREES && a < R) leaves[cnt++] = a;
+                    bits &= bits - 1;
+                }
+            }
+            *count = cnt;
+        }
+        __syncthreads();
+        const int cnt = *count;
+        for (int i = tid; i < R; i += ACQ_COND_THREADS) {
+            const double *row = Mb + (size_t)i * R;
+            double s = 0.0;
+            for (int k = 0; k < cnt; ++k) s += row[leaves[k]];
+            t[i] = s;
+        }
+        __syncthreads();
+        if (wave == 0) {
+            double v = lane < cnt ? t[leaves[lane]] : 0.0;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+            if (lane == 0) {
+                *qs = v;
+                double s = 0.0;
+                for (int k = 0; k < cnt; ++k) s += wb[leaves[k]];  // w as the previous point left it
+                const double mu = c * s;
+                const double var = scale[b] / (double)m * v + s2;
+                double ys;
+                if (mode == BARK_OBSERVE_VALUES) {
+                    ys = values[(size_t)b * value_stride + p];
+                } else {
+                    double e;
+                    if (eps) {
+                        e = eps[(size_t)b * P + p];
+                    } else {
+                        uint32_t x[4];
+                        philox(k0, k1, b0 + (uint32_t)b, draw, (uint32_t)(p >> 1), 0u, x);
+                        const double u1 = uniform53(x[0], x[1]), u2 = uniform53(x[2], x[3]);
+                        const double r = sqrt(-2.0 * log(1.0 - u1)), th = 6.283185307179586 * u2;
+                        e = (p & 1) ? r * sin(th) : r * cos(th);
+                    }
+                    ys = mu + sqrt(var) * e;
+                }
+                const double dy = ys - mu;
+                obs[0] = s;
+                obs[1] = dy / (1.0 + c * v);
+                obs[2] += -0.5 * (log(var) + dy * dy / var);
+                if (values_out) values_out[(size_t)b * P + p] = ys;
+            }
+        }
+        __syncthreads();
+        const double g = c / (1.0 + c * *qs);
+        const double dw = obs[1];
+        for (int i = tid; i < R; i += ACQ_COND_THREADS) wb[i] += t[i] * dw;
+        for (int i = wave; i < R; i += ACQ_COND_THREADS / 64) {
+            const double ti = t[i];
+            double *row = Mb + (size_t)i * R;
+            for (int j = lane; j < R; j += 64) row[j] -= g * (ti * t[j]);
+        }
+        __syncthreads();  // the next point reads the updated matrix and w, and reuses t, the leaf list and q, s, d
+    }
+    if (tid == 0 && logpred_out) logpred_out[b] = obs[2];
 }
 
 // Utility of the target kinds (include/bark_hip.h) for one candidate and forest: -(1/S) sum_s g(mu, sd, t_s), s = 0 .. S-1.
@@ -357,6 +471,7 @@ __global__ __launch_bounds__(256) void acq_best_kernel(const double *__restrict_
 }
 
 size_t acq_condition_lds_bytes(int64_t R) { return ((size_t)R + 1) * sizeof(double) + (ACQ_MAX_TREES + 2) * sizeof(int); }
+size_t acq_observe_lds_bytes(int64_t R) { return acq_condition_lds_bytes(R) + 3 * sizeof(double); }
 
 // the instantiation of a variant and kind; both confidence bounds share one (they differ in the finish only)
 using ScanKernel = decltype(&acq_scan_kernel<true, BARK_ACQ_LCB_MEAN>);
@@ -370,15 +485,16 @@ ScanKernel scan_kernel(bool lds, int kind) {
 }
 
 // The kernels of this unit that can use more than 64 KiB of dynamic LDS: the LDS variant of the scan, every kind (up to a whole CU's),
-// and acq_condition_kernel at the largest R the leaf-space path admits (8192: 264 bytes past 64 KiB).  acq_condition and
-// acq_scan call this before they launch.
+// and acq_condition_kernel / acq_observe_kernel at the largest R the leaf-space path admits (8192: 264 / 288 bytes past
+// 64 KiB).  acq_condition, acq_observe and acq_scan call this before they launch.
 int raise_acq_lds_limits() {
     static const LdsLimit limits[] = {{reinterpret_cast<const void *>(scan_kernel(true, BARK_ACQ_LCB_MEAN)), ACQ_LDS_MAX},
                                       {reinterpret_cast<const void *>(scan_kernel(true, BARK_ACQ_EI)), ACQ_LDS_MAX},
                                       {reinterpret_cast<const void *>(scan_kernel(true, BARK_ACQ_PI)), ACQ_LDS_MAX},
                                       {reinterpret_cast<const void *>(scan_kernel(true, BARK_ACQ_MES)), ACQ_LDS_MAX},
                                       {reinterpret_cast<const void *>(acq_condition_kernel), acq_condition_lds_bytes(8192)},
-                                      {reinterpret_cast<const void *>(acq_condition_from_kernel), acq_condition_lds_bytes(8192)}};
+                                      {reinterpret_cast<const void *>(acq_condition_from_kernel), acq_condition_lds_bytes(8192)},
+                                      {reinterpret_cast<const void *>(acq_observe_kernel), acq_observe_lds_bytes(8192)}};
     static LdsLimitsOnce once;
     return raise_lds_limits(once, limits);
 }
@@ -410,6 +526,19 @@ int acq_condition_from(const uint32_t *pcodes, int W, int ppad, int P, const dou
     if (rc) return rc;
     hipLaunchKernelGGL(acq_condition_from_kernel, dim3((unsigned)bc), dim3(ACQ_COND_THREADS), acq_condition_lds_bytes(R), s, pcodes,
                        W, ppad, P, src, dst, R, noise, scale, m, info);
+    BARK_LAUNCH_CHECK();
+    return BARK_OK;
+}
+
+// M^-1 and w of the chunk's forests conditioned on the P points with values (acq_observe_kernel); b0: the chunk's first forest
+int acq_observe(const uint32_t *pcodes, int W, int ppad, int P, double *Minv, double *w, int R, const double *noise,
+                const double *scale, int m, int bc, const int32_t *info, int mode, const double *values, int value_stride,
+                const double *eps, uint64_t seed, int64_t b0, int64_t draw, double *values_out, double *logpred_out, hipStream_t s) {
+    const int rc = raise_acq_lds_limits();
+    if (rc) return rc;
+    hipLaunchKernelGGL(acq_observe_kernel, dim3((unsigned)bc), dim3(ACQ_COND_THREADS), acq_observe_lds_bytes(R), s, pcodes, W, ppad, P,
+                       Minv, w, R, noise, scale, m, info, mode, values, value_stride, eps, (uint32_t)seed,
+                       (uint32_t)(seed >> 32) ^ OBSERVE_KEY, (uint32_t)b0, (uint32_t)draw, values_out, logpred_out);
     BARK_LAUNCH_CHECK();
     return BARK_OK;
 }

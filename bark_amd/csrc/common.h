@@ -175,6 +175,11 @@ int acq_condition(const uint32_t *pcodes, int W, int ppad, int P, double *Minv, 
 // ... out of place (P >= 1): dst (bc, R, R) = src conditioned; src, e.g. a fitted state, is only read
 int acq_condition_from(const uint32_t *pcodes, int W, int ppad, int P, const double *src, double *dst, int R, const double *noise,
                        const double *scale, int m, int bc, const int32_t *info, hipStream_t s);
+// M^-1 and w (bc, R) conditioned in place on the P points with values (include/bark_hip.h, bark_leaf_posterior_observe_hip):
+// values / eps / values_out / logpred_out are the chunk's rows, b0 its first forest (for the Philox counter)
+int acq_observe(const uint32_t *pcodes, int W, int ppad, int P, double *Minv, double *w, int R, const double *noise,
+                const double *scale, int m, int bc, const int32_t *info, int mode, const double *values, int value_stride,
+                const double *eps, uint64_t seed, int64_t b0, int64_t draw, double *values_out, double *logpred_out, hipStream_t s);
 // image of the chunk for the LDS variant
 int acq_pack(const double *Minv, const double *w, int R, int bc, double *tab, hipStream_t s);
 // variant: 1 LDS, 2 global (resolved by bark_acquisition_plan); n candidates of one slab against the bc forests of the chunk;

@@ -718,6 +718,49 @@ int bark_leaf_posterior_condition_hip(bark_ctx *ctx, const void *packed, const b
     return fc.copy_info(st.info, info_out, (int)fc.B);
 }
 
+size_t bark_leaf_posterior_observe_workspace_bytes(int64_t max_bits, int64_t m, int64_t Bc, int64_t P) {
+    return bark_leaf_posterior_condition_workspace_bytes(max_bits, m, Bc, P);
+}
+
+// The state conditioned in place on P more points with values, in the order given (acq_observe_kernel on the state's M^-1 and
+// w): bark_leaf_posterior_condition_hip's checks, chunks, walk and fault handling.  The values stay on the device: they are
+// not read back, so a NaN value gives a NaN w and no status.
+int bark_leaf_posterior_observe_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, int64_t d, const double *noise,
+                                    const double *scale, const double *points, int64_t P, const double *values, int64_t value_stride,
+                                    int mode, const double *eps, uint64_t seed, int64_t draw, void *state, size_t state_bytes,
+                                    double *values_out, double *logpred_out, int32_t *info_out, void *workspace,
+                                    size_t workspace_bytes, int64_t Bc, void *stream_) {
+    static const char *name = "bark_leaf_posterior_observe_hip";
+    error_buffer()[0] = 0;
+    if (!info) return fail(BARK_ERR_ARG, "%s: null argument", name);
+    if (P < 0 || P > ACQ_MAX_PENDING)
+        return fail(BARK_ERR_ARG, "%s: at most %lld points per call (got %lld)", name, (long long)ACQ_MAX_PENDING, (long long)P);
+    if (P > 0 && !points) return fail(BARK_ERR_ARG, "%s: null argument", name);
+    if (mode != BARK_OBSERVE_VALUES && mode != BARK_OBSERVE_SAMPLE) return fail(BARK_ERR_ARG, "%s: unknown mode %d", name, mode);
+    if (mode == BARK_OBSERVE_VALUES && !values) return fail(BARK_ERR_ARG, "%s: BARK_OBSERVE_VALUES needs values", name);
+    if (value_stride != 0 && value_stride != P)
+        return fail(BARK_ERR_ARG, "%s: value_stride is 0 (one vector for all forests) or P (got %lld)", name, (long long)value_stride);
+    if (draw < 0 || draw > 0xFFFFFFFFll) return fail(BARK_ERR_ARG, "%s: draw number outside 0 .. 2^32 - 1", name);
+    FittedCall fc;
+    int rc;
+    if ((rc = fc.open(name, ctx, packed, info, d, noise, scale, state, state_bytes, info_out, workspace, Bc, stream_))) return rc;
+    const FittedAreas a = fitted_areas(workspace, fc.R, fc.Bc, 0, P, false, false);
+    if (workspace_bytes < a.total) return fail(BARK_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, a.total);
+    const PosteriorState &st = fc.st;
+    for (int64_t c0 = 0; P > 0 && c0 < fc.B; c0 += fc.Bc) {
+        const int bc = (int)(fc.B - c0 < fc.Bc ? fc.B - c0 : fc.Bc);
+        bark_pack_info sub;
+        const char *packed_c = fc.chunk(c0, bc, sub);
+        if ((rc = walk_one_hot(packed_c, &sub, points, P, fc.d, (int)a.W, a.pcodes, ctx->fault, fc.caller))) return rc;
+        rc = acq_observe(a.pcodes, (int)a.W, (int)a.ppad, (int)P, st.Minv + (size_t)c0 * fc.R * fc.R, st.w + (size_t)c0 * fc.R, fc.R,
+                         noise + c0, scale + c0, fc.m, bc, st.info + c0, mode, values ? values + (size_t)c0 * value_stride : nullptr,
+                         (int)value_stride, eps ? eps + (size_t)c0 * P : nullptr, seed, c0, draw,
+                         values_out ? values_out + (size_t)c0 * P : nullptr, logpred_out ? logpred_out + c0 : nullptr, fc.caller);
+        if (rc || (rc = fc.fault_info(st.info + c0, bc))) return rc;
+    }
+    return fc.copy_info(st.info, info_out, (int)fc.B);
+}
+
 // Predictive scores (include/bark_hip.h, kernels in scores.hip): the scan's sequence with the points in place of the
 // candidates; the per-forest rows are finished chunk by chunk, the mixture after the last chunk.
 int bark_predictive_scores_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, const double *X, int64_t N,

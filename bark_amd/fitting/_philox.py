@@ -42,11 +42,10 @@ def uniforms(seed: int, chain, tree, sweep: int, n_draws: int) -> np.ndarray:
 PATH_KEY = 0x70617468  # "path": csrc/paths.hip xors it into the key's high word
 
 
-def path_normals(seed: int, forest, draw, R: int) -> np.ndarray:
-    """The standard normals of the sample paths (forest[i], draw[i]) -> (len(forest), R), as csrc/paths.hip draws them when
-    no eps is given: key = (seed low word, seed high word ^ PATH_KEY), counter = (forest, draw, a // 2, 0) for entry a; with
-    u1, u2 the block's two uniforms, r = sqrt(-2 log(1 - u1)) and th = 6.283185307179586 u2, the even entry is r cos th and
-    the odd one r sin th.  A row depends on (seed, forest, draw) only."""
+def _keyed_normals(key_xor: int, seed: int, forest, draw, R: int) -> np.ndarray:
+    """Box-Muller normals (len(forest), R): key = (seed low word, seed high word ^ key_xor), counter = (forest, draw, a // 2, 0)
+    for entry a; with u1, u2 the block's two uniforms, r = sqrt(-2 log(1 - u1)) and th = 6.283185307179586 u2, the even entry
+    is r cos th and the odd one r sin th."""
     forest = np.asarray(forest, dtype=np.uint64).reshape(-1)
     draw = np.broadcast_to(np.asarray(draw, dtype=np.uint64).reshape(-1), forest.shape)
     half = (int(R) + 1) // 2
@@ -54,8 +53,26 @@ def path_normals(seed: int, forest, draw, R: int) -> np.ndarray:
     ctr[..., 0], ctr[..., 1] = forest[:, None], draw[:, None]
     ctr[..., 2] = np.arange(half, dtype=np.uint64)[None, :]
     seed = int(seed) & (2 ** 64 - 1)
-    words = philox4x32((seed & 0xFFFFFFFF, ((seed >> 32) & 0xFFFFFFFF) ^ PATH_KEY), ctr).astype(np.uint64)
+    words = philox4x32((seed & 0xFFFFFFFF, ((seed >> 32) & 0xFFFFFFFF) ^ key_xor), ctr).astype(np.uint64)
     u1 = ((words[..., 0] | (words[..., 1] << _S32)) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
     u2 = ((words[..., 2] | (words[..., 3] << _S32)) >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
     r, th = np.sqrt(-2.0 * np.log(1.0 - u1)), 6.283185307179586 * u2
     return np.stack([r * np.cos(th), r * np.sin(th)], axis=-1).reshape(forest.shape[0], 2 * half)[:, :int(R)]
+
+
+def path_normals(seed: int, forest, draw, R: int) -> np.ndarray:
+    """The standard normals of the sample paths (forest[i], draw[i]) -> (len(forest), R), as csrc/paths.hip draws them when
+    no eps is given: key = (seed low word, seed high word ^ PATH_KEY), counter = (forest, draw, a // 2, 0) for entry a; with
+    u1, u2 the block's two uniforms, r = sqrt(-2 log(1 - u1)) and th = 6.283185307179586 u2, the even entry is r cos th and
+    the odd one r sin th.  A row depends on (seed, forest, draw) only."""
+    return _keyed_normals(PATH_KEY, seed, forest, draw, R)
+
+
+FANTASY_KEY = 0x66616E74  # "fant": acq_observe_kernel (csrc/acquire.hip) xors it into the key's high word
+
+
+def fantasy_normals(seed: int, forest, draw, P: int) -> np.ndarray:
+    """The standard normals of the sampled fantasies (forest[i], draw[i]) at P points -> (len(forest), P), as
+    csrc/acquire.hip draws them when no eps is given: `path_normals` with FANTASY_KEY in place of PATH_KEY, entry p for
+    point p of the call.  A row depends on (seed, forest, draw) only."""
+    return _keyed_normals(FANTASY_KEY, seed, forest, draw, P)

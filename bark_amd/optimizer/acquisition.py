@@ -208,7 +208,8 @@ def propose_from_candidates(model, data, candidates, domain, kappa: float = 1.96
 
 
 def propose_batch_from_candidates(model, data, candidates, domain, q: int, kappa: float = 1.96, kind: str = "lcb_mean",
-                                  pending=None, chunk: int | None = None, variant: str = "auto", targets=None, posterior=None):
+                                  pending=None, chunk: int | None = None, variant: str = "auto", targets=None, posterior=None,
+                                  fantasy="mean", seed: int = 0):
     """-> (rows (q, d), indices (q,)): q distinct candidate rows chosen greedily.  Pick k is the arg-min of the scan
     conditioned on `pending` followed by picks 0 .. k-1 (`acquisition_scan(pending=..., skip=...)`), with those picks
     excluded: a point that is being evaluated no longer attracts the next one, because its variance has collapsed.
@@ -219,7 +220,23 @@ def propose_batch_from_candidates(model, data, candidates, domain, q: int, kappa
     None) a private copy of its state is conditioned once on `pending` and once on every pick (`LeafPosterior.condition_`),
     and the scans pass only the picks to skip: nothing is refitted, one downdate per forest and pick, the same rows and indices.
     Torch candidates give device tensors (a pick is gathered with index_select; no index is read back), numpy candidates
-    numpy arrays.  ValueError for q < 1, q > C or P + q - 1 > 64 (the scan's limit on pending points), on both routes."""
+    numpy arrays.  ValueError for q < 1, q > C or P + q - 1 > 64 (the scan's limit on pending points), on both routes.
+
+    fantasy: what a point in flight is taken to return.  "mean" (the default, everything above): each forest's own posterior
+    mean, the kriging believer.  A float: that constant for every forest, the constant liar (`min(y)` and `mean(y)` are the
+    usual ones).  "sample": a draw from each forest's own predictive (`LeafPosterior.fantasise`), pick k with the draw number
+    k and the initial `pending` points with the draw number q, all under `seed` — over kind="ei" the usual Monte-Carlo
+    batch.  The pending points take the same fantasy as the picks.  The last two move w as well as M^-1, which only a fitted
+    state can do: they need `posterior=` (ValueError otherwise)."""
+    if isinstance(fantasy, str):
+        if fantasy not in ("mean", "sample"):
+            raise ValueError(f"unknown fantasy {fantasy!r} (use 'mean', 'sample' or a float)")
+    else:
+        fantasy = float(fantasy)
+        if not math.isfinite(fantasy):
+            raise ValueError(f"a constant fantasy must be finite, got {fantasy}")
+    if fantasy != "mean" and posterior is None:
+        raise ValueError("fantasy other than 'mean' needs a fitted state: pass posterior=fit_posterior(model, data, domain)")
     C = len(candidates)
     q = int(q)
     P = 0 if pending is None else len(pending)
@@ -237,7 +254,15 @@ def propose_batch_from_candidates(model, data, candidates, domain, q: int, kappa
         pend = None if P == 0 else np.asarray(pending.cpu() if _is_torch(pending) else pending, dtype=np.float64)
     rows, picks = [], []
     if posterior is not None:
-        post = _fitted(posterior, domain).condition(pend)  # a copy, also when there is nothing to condition on
+        def fantasised(post, points, draw):
+            if fantasy == "sample":
+                post._fantasise_(points, seed, draw)
+            else:
+                post.condition_(points, None if fantasy == "mean" else fantasy)
+
+        post = _fitted(posterior, domain)._copy()  # also when there is nothing to condition on
+        if pend is not None:
+            fantasised(post, pend, q)
         for k in range(q):
             skip = None if not picks else torch.stack(picks) if on_device else picks
             _, idx = post.scan(candidates, kappa=kappa, kind=kind, chunk=chunk, variant=variant, skip=skip, targets=targets)
@@ -248,7 +273,7 @@ def propose_batch_from_candidates(model, data, candidates, domain, q: int, kappa
                 rows.append(candidates[idx])
             picks.append(idx)
             if k + 1 < q:
-                post.condition_(rows[-1].reshape(1, -1))
+                fantasised(post, rows[-1].reshape(1, -1), k)
         if on_device:
             return torch.stack(rows), torch.stack(picks)
         return np.stack(rows), np.asarray(picks, dtype=np.int64)

@@ -3,8 +3,9 @@
 Every call of `bark_amd.optimizer.acquisition_scan` packs the forests, walks the N training points, forms and factorises
 I + c Z'Z for every forest, solves for w and M^-1, scores the candidates and throws all of that away.  `fit_posterior` does
 the part that does not depend on the candidates (bark_leaf_posterior_fit_hip) and returns a `LeafPosterior` that owns the
-result; its `scan` is the same scan from that state (bark_acquisition_scan_fitted_hip) and `condition` is the step a greedy
-batch takes between two picks (bark_leaf_posterior_condition_hip).  include/bark_hip.h has the contract: a scan from the
+result; its `scan` is the same scan from that state (bark_acquisition_scan_fitted_hip), `condition` is the step a greedy
+batch takes between two picks (bark_leaf_posterior_condition_hip), and `observe` / `fantasise` / `log_predictive` move the
+state forward on points with observed or sampled values (bark_leaf_posterior_observe_hip).  include/bark_hip.h has the contract: a scan from the
 state returns the bits of the stateless scan that uses the `chunk` the state was fitted with.
 """
 
@@ -113,26 +114,142 @@ class LeafPosterior:
         out = (float(best.item()), int(idx.item()))
         return (*out, acq.cpu().numpy()) if return_values else out
 
-    def condition_(self, points) -> "LeafPosterior":
+    def condition_(self, points, values=None) -> "LeafPosterior":
         """Condition the state in place on `points` (P <= 64, d), in the order given, as `acquisition_scan(pending=points)`
         conditions its own M^-1: one rank-one downdate per point and forest, w unchanged.  A later `scan()` equals the
         stateless scan with these pending points, bit for bit; conditioning twice equals once on the concatenation.  After a
-        ValueError for an invalid categorical value the state is marked failed (`info` = -1)."""
+        ValueError for an invalid categorical value the state is marked failed (`info` = -1).
+
+        values=None is that call, the kriging believer.  Otherwise the points are fantasised at `values` — a float (the
+        constant liar), a (P,) array shared by the forests or a (B, P) array — and w moves with them
+        (bark_leaf_posterior_observe_hip); M^-1 ends with the same bits either way.  These are fantasies: `N` and
+        `train_y_min` stay as they are (`observe_` is the call for data)."""
         if points is None or len(points) == 0:
             return self
         pend_d = _points(points, self.d)[0]
         P = int(pend_d.shape[0])
         if P > MAX_PENDING:
             raise ValueError(f"at most {MAX_PENDING} pending points per call (got {P})")
+        if values is not None:
+            self._observe(pend_d, self._values(values, P, forests=True))
+            return self
         lib = _lib.lib()
         self._call(lib.bark_leaf_posterior_condition_hip,
                    lambda k: int(lib.bark_leaf_posterior_condition_workspace_bytes(self.R, self.m, k, P)), None,
                    _lib.ptr(pend_d), P, _lib.ptr(self.state), self.nbytes)
         return self
 
-    def condition(self, points) -> "LeafPosterior":
+    def condition(self, points, values=None) -> "LeafPosterior":
         """A new LeafPosterior conditioned on `points` (`condition_`): it shares the forests and owns a copy of the state."""
-        return self._copy().condition_(points)
+        return self._copy().condition_(points, values)
+
+    def _values(self, values, P: int, forests: bool):
+        """values of P points as a float64 device tensor: (P,), or with `forests` also a scalar (-> (P,)) or (B, P); with
+        `forests` False also (P, 1), and the entries must be finite."""
+        import torch
+
+        if forests and np.ndim(values) == 0:  # a float, or a 0-d array or tensor
+            values = np.full(P, float(values))
+        v = _lib.to_device(values.detach() if _is_torch(values) else np.asarray(values, dtype=np.float64), torch.float64)
+        if not forests and v.ndim == 2 and v.shape[1] == 1:
+            v = v.reshape(-1)
+        ok = tuple(v.shape) == (P,) or (forests and tuple(v.shape) == (self.B, P))
+        if not ok:
+            want = f"a float, ({P},) or ({self.B}, {P})" if forests else f"({P},) or ({P}, 1)"
+            raise ValueError(f"values must be {want}, got {tuple(v.shape)}")
+        if not forests and not bool(torch.isfinite(v).all()):
+            raise ValueError("observed values must be finite")
+        return v
+
+    def _observe(self, pend_d, values_d=None, *, eps_d=None, seed: int = 0, draw: int = 0, values_out=None, logpred_out=None,
+                 chunk=None):
+        """One call of bark_leaf_posterior_observe_hip on the state: pend_d (P <= 64, d) on the device, with values_d ((P,)
+        or (B, P)) or, without them, sampled fantasies (eps_d (B, P) or Philox draws named by seed and draw)."""
+        import ctypes
+
+        P = int(pend_d.shape[0])
+        lib = _lib.lib()
+        stride = 0 if values_d is None or values_d.ndim == 1 else P
+        self._call(lib.bark_leaf_posterior_observe_hip,
+                   lambda k: int(lib.bark_leaf_posterior_observe_workspace_bytes(self.R, self.m, k, P)), chunk,
+                   _lib.ptr(pend_d), P, _lib.ptr(values_d), stride, _lib.OBSERVE_SAMPLE if values_d is None else _lib.OBSERVE_VALUES,
+                   _lib.ptr(eps_d), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), int(draw), _lib.ptr(self.state), self.nbytes,
+                   _lib.ptr(values_out), _lib.ptr(logpred_out))
+
+    def observe_(self, points, values, chunk: int | None = None) -> "LeafPosterior":
+        """Take in real observations: the state becomes, to rounding, what `fit_posterior` gives on the data plus
+        (`points`, `values`), by one rank-one step per point and forest on M^-1 and w instead of a refit
+        (bark_leaf_posterior_observe_hip).  values: (P,) or (P, 1), finite, else ValueError.  More than 64 points are applied
+        in slices of 64, in order.  Sets N += P and train_y_min = min(train_y_min, values.min()); everything that reads the
+        state (`scan`, `sample_paths`, the `propose_*` functions) follows.  Returns self.  After a ValueError for an invalid
+        categorical value the state is marked failed (`info` = -1).  chunk: forests per launch; it bounds the workspace and
+        changes no bit, here and in `fantasise` and `log_predictive`."""
+        if points is None or len(points) == 0:
+            return self
+        pend_d = _points(points, self.d)[0]
+        P = int(pend_d.shape[0])
+        v = self._values(values, P, forests=False)
+        for p0 in range(0, P, MAX_PENDING):
+            self._observe(pend_d[p0:p0 + MAX_PENDING], v[p0:p0 + MAX_PENDING], chunk=chunk)
+        self.N += P
+        self.train_y_min = min(self.train_y_min, float(v.min()))
+        return self
+
+    def observe(self, points, values, chunk: int | None = None) -> "LeafPosterior":
+        """A new LeafPosterior that has taken in the observations (`observe_`): it shares the forests and owns a copy of the
+        state."""
+        return self._copy().observe_(points, values, chunk)
+
+    def fantasise(self, points, seed: int = 0, draw: int = 0, eps=None, chunk: int | None = None):
+        """-> (LeafPosterior, values (B, P)): a copy conditioned on `points` (P <= 64) at values drawn from each forest's own
+        predictive, point by point, each draw seeing the ones before it: per forest the P values are one joint draw of the
+        noisy observations at the points.  eps: (B, P) standard normals, numpy or torch; without it Philox draws named by
+        (`seed`, forest, `draw`, p) alone (fitting/_philox.fantasy_normals restates them), so the same pair gives the same
+        fantasy whatever else is asked for; torch's generator is not used.  numpy points give a numpy array of values, torch
+        points a device tensor.  `N` and `train_y_min` are those of the original."""
+        new = self._copy()
+        return new, new._fantasise_(points, seed, draw, eps, chunk)
+
+    def _fantasise_(self, points, seed=0, draw=0, eps=None, chunk=None):
+        """`fantasise` in place -> the values (B, P)."""
+        import torch
+
+        for name, x in (("seed", seed), ("draw", draw)):
+            if isinstance(x, bool) or not isinstance(x, (int, np.integer)):
+                raise TypeError(f"{name} must be an int, got {type(x).__name__}")
+        if not 0 <= int(draw) < 2 ** 32:
+            raise ValueError(f"draw must lie in [0, 2^32), got {draw}")
+        pend_d = _points(points, self.d)[0]
+        P = int(pend_d.shape[0])
+        if P < 1 or P > MAX_PENDING:
+            raise ValueError(f"between 1 and {MAX_PENDING} points per call (got {P})")
+        eps_d = None
+        if eps is not None:
+            eps_d = _lib.to_device(eps.detach() if _is_torch(eps) else np.asarray(eps, dtype=np.float64), torch.float64)
+            if tuple(eps_d.shape) != (self.B, P):
+                raise ValueError(f"eps must be ({self.B}, {P}), got {tuple(eps_d.shape)}")
+        out = torch.empty((self.B, P), dtype=torch.float64, device=self.state.device)
+        self._observe(pend_d, eps_d=eps_d, seed=int(seed), draw=int(draw), values_out=out, chunk=chunk)
+        return out if _is_torch(points) else out.cpu().numpy()
+
+    def log_predictive(self, points, values, chunk: int | None = None):
+        """-> (B,): per forest the log density of `values` ((P,) or (P, 1), finite) at `points` under the state's predictive,
+        one step ahead point by point — log p(y_1) + log p(y_2 | y_1) + ... without the 2 pi terms, which equals
+        MLL(data + new) - MLL(data) in the convention of `batched_mll(include_2pi=False)`.  Computed on a scratch copy of
+        the state by the update `observe_` applies; the state is not modified.  numpy points give numpy, torch points a device
+        tensor."""
+        import torch
+
+        total = torch.zeros(self.B, dtype=torch.float64, device=self.state.device)
+        if points is not None and len(points) > 0:
+            pend_d = _points(points, self.d)[0]
+            P = int(pend_d.shape[0])
+            v = self._values(values, P, forests=False)
+            scratch, part = self._copy(), torch.empty_like(total)
+            for p0 in range(0, P, MAX_PENDING):
+                scratch._observe(pend_d[p0:p0 + MAX_PENDING], v[p0:p0 + MAX_PENDING], logpred_out=part, chunk=chunk)
+                total += part
+        return total if _is_torch(points) else total.cpu().numpy()
 
     def sample_paths(self, num_samples: int = 1, *, forests=None, seed: int = 0, eps=None) -> LeafPaths:
         """Posterior sample paths from the state (bark_leaf_posterior_paths_hip): for path (b, s) the leaf weights

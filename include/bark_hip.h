@@ -484,6 +484,29 @@ int bark_acquisition_scan_targets_hip(bark_ctx *ctx, const void *packed, const b
  *   0 <= P <= 64 per call.  An invalid categorical value in a point sets info_out and the state's status to -1: that state's
  *   M^-1 is no longer meaningful.  Forests whose status is non-zero are left alone.
  *   workspace >= bark_leaf_posterior_condition_workspace_bytes(R, m, Bc, P): the pending codes.
+ * bark_leaf_posterior_observe_hip: the state conditioned in place on P more points WITH values — observations or fantasies —
+ *   in the order given.  Per forest and point, z the one-hot row of the point, every update seeing the ones before it:
+ *       t = M^-1 z        q = z't        s = z'w        mu = c s        v = (scale / m) q + s2     (predictive of the observation)
+ *       w <- w + t (y* - mu) / (1 + c q)        M^-1 <- M^-1 - (c / (1 + c q)) t t'        logpred += -1/2 ( log v + (y* - mu)^2 / v )
+ *   which is exactly the state a refit on the data plus (points, y*) gives, and logpred = MLL(data + new) - MLL(data) in the
+ *   convention without the 2 pi term.  t, q and the rewrite of M^-1 are the condition call's operations in its order, so M^-1
+ *   ends with the bits bark_leaf_posterior_condition_hip leaves; s sums w over the point's leaves in code-bit order from 0.0
+ *   (the scan's order for mu).  y* of point p under forest b, by mode:
+ *     BARK_OBSERVE_VALUES  values[b value_stride + p]: value_stride = 0 for one (P,) vector shared by all forests, P for (B, P).
+ *       With y* = mu this is the condition call; a constant is the "constant liar".
+ *     BARK_OBSERVE_SAMPLE  mu + sqrt(v) e: by the chain rule the P values are one joint draw from the forest's predictive at
+ *       the P points (noise included).  e = eps[b P + p] when eps (B, P) is given; otherwise Box-Muller on Philox4x32-10 with
+ *       key = (seed low word, seed high word ^ 0x66616E74 "fant") and counter = (b, draw, p / 2, 0), u1 / u2 / r / th as for the
+ *       sample paths below: even p takes r cos th, odd p takes r sin th.  A fantasy is a function of (seed, b, draw, p) and
+ *       the state only, not of Bc.  values is ignored in this mode.
+ *   values_out (B, P) or NULL: the values used.  logpred_out (B,) or NULL: logpred summed over p = 0 .. P-1 in that order.
+ *   Forests whose status is non-zero are left alone and their rows of both outputs are NaN.  The values are not read back: a
+ *   NaN or infinite value gives a NaN w and nothing is reported.  An invalid categorical value in a point sets info_out and
+ *   the state's status to -1, as for the condition call.  0 <= P <= 64 per call; P = 0 launches nothing but the copy of the
+ *   status into info_out and writes neither output.  0 <= draw < 2^32.
+ *   workspace >= bark_leaf_posterior_observe_workspace_bytes(R, m, Bc, P): the codes of the points.
+ *   Refused with BARK_ERR_ARG before any launch, beside the limits below: points == NULL with P > 0, an unknown mode,
+ *   BARK_OBSERVE_VALUES without values, a value_stride other than 0 or P.
  * Limits, refused with BARK_ERR_ARG before any launch: those of bark_acquisition_scan_targets_hip; a state buffer smaller
  * than bark_leaf_posterior_bytes or not 256-byte aligned.  The calls only enqueue; the queries are pure host code.
  * ------------------------------------------------------------------------------------- */
@@ -506,6 +529,16 @@ int bark_leaf_posterior_condition_hip(bark_ctx *ctx, const void *packed, const b
                                       const double *scale, const double *pending /* (P, d) */, int64_t P, void *state,
                                       size_t state_bytes, int32_t *info_out /* (B,) */, void *workspace, size_t workspace_bytes,
                                       int64_t Bc, void *stream);
+#define BARK_OBSERVE_VALUES 0
+#define BARK_OBSERVE_SAMPLE 1
+size_t bark_leaf_posterior_observe_workspace_bytes(int64_t max_bits, int64_t m, int64_t Bc, int64_t P);
+int bark_leaf_posterior_observe_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, int64_t d, const double *noise,
+                                    const double *scale, const double *points /* (P, d) */, int64_t P,
+                                    const double *values /* (P,) or (B, P) or NULL */, int64_t value_stride, int mode,
+                                    const double *eps /* (B, P) or NULL */, uint64_t seed, int64_t draw, void *state,
+                                    size_t state_bytes, double *values_out /* (B, P) or NULL */,
+                                    double *logpred_out /* (B,) or NULL */, int32_t *info_out /* (B,) */, void *workspace,
+                                    size_t workspace_bytes, int64_t Bc, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Sample paths from a fitted posterior (Thompson sampling).  A tree kernel has finite rank, so a posterior draw of forest b
