@@ -14,6 +14,8 @@
 //                       registers (sum of mu - kappa sd, of mu, of var + mu^2), kept in a (3, C) buffer between chunks
 //                       the target kinds (EI, PI, MES) instead keep one sum, of -(1/S) sum_s g(mu, sd, t_{b,s}), the
 //                       S targets of the forest read through wave-uniform addresses
+//                       with importance weights (the scan from a fitted state only) each forest's terms are multiplied by
+//                       its normalised weight and a forest of weight 0 is skipped: instantiations of their own
 //   acq_finish_kernel   the acquisition value per candidate and per-workgroup (value, lowest index) minima;
 //   acq_best_kernel     reduces those (no float atomics: ties go to the lowest candidate index)
 // The order of every sum is fixed (leaves in code-bit order, targets 0 .. S-1, forests 0 .. B-1), so the result depends neither on the chunk
@@ -328,13 +330,17 @@ __device__ __forceinline__ double acq_target_term(double mu, double var, const d
 // n: candidates of this slab (ccodes (bc, W, cpad) holds their codes), acc: the slab's part of the (3, C) sums, row stride
 // `astride`; first: this is the first chunk of forests (the sums start at zero).
 // KIND: BARK_ACQ_LCB_MEAN for both confidence bounds (three sums; kappa), or a target kind (row 0 of acc only; targets (bc, S)).
-template <bool LDS_TABLE, int KIND>
+// WEIGHTED: every term of forest b enters its sum multiplied by weights[b] (the chunk's rows of the caller's normalised
+// importance weights; one address per forest, the same in all lanes, so it loads like noise[b]), and a forest whose weight is
+// exactly 0 is skipped whole.  Without it `weights` is not read and the code is the equal-weight scan, unchanged.
+template <bool LDS_TABLE, int KIND, bool WEIGHTED>
 __global__ __launch_bounds__(ACQ_TILE) void acq_scan_kernel(const uint32_t *__restrict__ ccodes, int W, int cpad, int n,
                                                             const double *__restrict__ wvec, const double *__restrict__ Minv,
                                                             const double *__restrict__ tab, int R,
                                                             const double *__restrict__ noise, const double *__restrict__ scale,
                                                             int m, int bc, double kappa, const double *__restrict__ targets,
-                                                            int S, int first, double *__restrict__ acc, size_t astride) {
+                                                            int S, int first, double *__restrict__ acc, size_t astride,
+                                                            const double *__restrict__ weights) {
     constexpr bool LCB = KIND == BARK_ACQ_LCB_MEAN;
     extern __shared__ double smem[];
     const int tid = threadIdx.x;
@@ -351,6 +357,13 @@ __global__ __launch_bounds__(ACQ_TILE) void acq_scan_kernel(const uint32_t *__re
         }
     }
     for (int b = 0; b < bc; ++b) {
+        double wt = 1.0;
+        if (WEIGHTED) {
+            // b and weights[b] are uniform over the workgroup: every thread takes this branch together, so the two barriers
+            // below are skipped by all of them or by none.  No table staging, no leaf lists, no arithmetic for the forest.
+            wt = weights[b];
+            if (wt == 0.0) continue;
+        }
         if (LDS_TABLE) {
             __syncthreads();  // the previous forest's reads are done
             stage_table(tab, b, tri, R, smem);
@@ -366,11 +379,14 @@ __global__ __launch_bounds__(ACQ_TILE) void acq_scan_kernel(const uint32_t *__re
         const double mu = sc / ((double)m * sigma2) * s1;
         const double var = sc / (double)m * (dg + 2.0 * off);
         if (LCB) {
-            a0 += mu - kappa * sqrt(var > 0.0 ? var : 0.0);
-            a1 += mu;
-            a2 += var + mu * mu;
+            const double t0 = mu - kappa * sqrt(var > 0.0 ? var : 0.0);
+            const double t2 = var + mu * mu;
+            a0 += WEIGHTED ? wt * t0 : t0;
+            a1 += WEIGHTED ? wt * mu : mu;
+            a2 += WEIGHTED ? wt * t2 : t2;
         } else {
-            a0 += acq_target_term<KIND>(mu, var, targets + (size_t)b * S, S);
+            const double t0 = acq_target_term<KIND>(mu, var, targets + (size_t)b * S, S);
+            a0 += WEIGHTED ? wt * t0 : t0;
         }
     }
     if (active) {
@@ -414,7 +430,8 @@ constexpr long long ACQ_NO_INDEX = 0x7fffffffffffffffLL;
 // kind 1: the lower confidence bound of the moment-matched mixture (tree_gps.py:116-131);
 // the target kinds: mean over the forests of the scan's one sum, like kind 0
 // skip (n_skip entries): candidates that keep their value in acq_out but never win the minimum
-__global__ __launch_bounds__(256) void acq_finish_kernel(const double *__restrict__ acc, long long C, int B, double kappa,
+// weighted: the sums already carry normalised weights (acq_scan_kernel<.., .., true>), so nothing is divided by B
+__global__ __launch_bounds__(256) void acq_finish_kernel(const double *__restrict__ acc, long long C, int B, int weighted, double kappa,
                                                          int kind, const long long *__restrict__ skip, int n_skip,
                                                          double *__restrict__ acq_out, double *__restrict__ part_v,
                                                          long long *__restrict__ part_i) {
@@ -425,10 +442,10 @@ __global__ __launch_bounds__(256) void acq_finish_kernel(const double *__restric
     long long i = ACQ_NO_INDEX;
     if (c < C) {
         if (kind != BARK_ACQ_LCB_MIXTURE) {
-            v = acc[c] / (double)B;
+            v = weighted ? acc[c] : acc[c] / (double)B;
         } else {
-            const double mu = acc[C + c] / (double)B;
-            const double var = acc[2 * C + c] / (double)B - mu * mu;
+            const double mu = weighted ? acc[C + c] : acc[C + c] / (double)B;
+            const double var = (weighted ? acc[2 * C + c] : acc[2 * C + c] / (double)B) - mu * mu;
             v = mu - kappa * sqrt(var > 0.0 ? var : 0.0);
         }
         if (acq_out) acq_out[c] = v;
@@ -447,10 +464,11 @@ __global__ __launch_bounds__(256) void acq_finish_kernel(const double *__restric
 }
 
 // one workgroup: the minimum over the partials; NaN / -1 when a forest of the call failed (info != 0), no value is finite or
-// every candidate was skipped
+// every candidate was skipped.  weights (B,) or null: a forest of weight exactly 0 took no part in the scan, so its status is ignored
 __global__ __launch_bounds__(256) void acq_best_kernel(const double *__restrict__ part_v, const long long *__restrict__ part_i,
                                                        int nblk, const int32_t *__restrict__ info, int B,
-                                                       double *__restrict__ best, long long *__restrict__ best_i) {
+                                                       const double *__restrict__ weights, double *__restrict__ best,
+                                                       long long *__restrict__ best_i) {
     __shared__ double rv[4];
     __shared__ long long ri[4];
     __shared__ int bad;
@@ -460,7 +478,7 @@ __global__ __launch_bounds__(256) void acq_best_kernel(const double *__restrict_
     long long i = ACQ_NO_INDEX;
     for (int k = threadIdx.x; k < nblk; k += 256) take_min(v, i, part_v[k], part_i[k]);
     int mine = 0;
-    for (int b = threadIdx.x; b < B; b += 256) mine |= info[b] != 0;
+    for (int b = threadIdx.x; b < B; b += 256) mine |= info[b] != 0 && (!weights || weights[b] != 0.0);
     if (mine) bad = 1;  // every writer stores the same value
     block_min(v, i, rv, ri);
     if (threadIdx.x == 0) {
@@ -474,14 +492,18 @@ size_t acq_condition_lds_bytes(int64_t R) { return ((size_t)R + 1) * sizeof(doub
 size_t acq_observe_lds_bytes(int64_t R) { return acq_condition_lds_bytes(R) + 3 * sizeof(double); }
 
 // the instantiation of a variant and kind; both confidence bounds share one (they differ in the finish only)
-using ScanKernel = decltype(&acq_scan_kernel<true, BARK_ACQ_LCB_MEAN>);
-ScanKernel scan_kernel(bool lds, int kind) {
+using ScanKernel = decltype(&acq_scan_kernel<true, BARK_ACQ_LCB_MEAN, false>);
+template <bool WEIGHTED> ScanKernel scan_kernel_of(bool lds, int kind) {
     switch (kind) {
-        case BARK_ACQ_EI: return lds ? acq_scan_kernel<true, BARK_ACQ_EI> : acq_scan_kernel<false, BARK_ACQ_EI>;
-        case BARK_ACQ_PI: return lds ? acq_scan_kernel<true, BARK_ACQ_PI> : acq_scan_kernel<false, BARK_ACQ_PI>;
-        case BARK_ACQ_MES: return lds ? acq_scan_kernel<true, BARK_ACQ_MES> : acq_scan_kernel<false, BARK_ACQ_MES>;
-        default: return lds ? acq_scan_kernel<true, BARK_ACQ_LCB_MEAN> : acq_scan_kernel<false, BARK_ACQ_LCB_MEAN>;
+        case BARK_ACQ_EI: return lds ? acq_scan_kernel<true, BARK_ACQ_EI, WEIGHTED> : acq_scan_kernel<false, BARK_ACQ_EI, WEIGHTED>;
+        case BARK_ACQ_PI: return lds ? acq_scan_kernel<true, BARK_ACQ_PI, WEIGHTED> : acq_scan_kernel<false, BARK_ACQ_PI, WEIGHTED>;
+        case BARK_ACQ_MES: return lds ? acq_scan_kernel<true, BARK_ACQ_MES, WEIGHTED> : acq_scan_kernel<false, BARK_ACQ_MES, WEIGHTED>;
+        default: return lds ? acq_scan_kernel<true, BARK_ACQ_LCB_MEAN, WEIGHTED> : acq_scan_kernel<false, BARK_ACQ_LCB_MEAN, WEIGHTED>;
     }
+}
+// the weighted scan has instantiations of its own, so the equal-weight ones keep their code
+ScanKernel scan_kernel(bool lds, int kind, bool weighted = false) {
+    return weighted ? scan_kernel_of<true>(lds, kind) : scan_kernel_of<false>(lds, kind);
 }
 
 // The kernels of this unit that can use more than 64 KiB of dynamic LDS: the LDS variant of the scan, every kind (up to a whole CU's),
@@ -492,6 +514,10 @@ int raise_acq_lds_limits() {
                                       {reinterpret_cast<const void *>(scan_kernel(true, BARK_ACQ_EI)), ACQ_LDS_MAX},
                                       {reinterpret_cast<const void *>(scan_kernel(true, BARK_ACQ_PI)), ACQ_LDS_MAX},
                                       {reinterpret_cast<const void *>(scan_kernel(true, BARK_ACQ_MES)), ACQ_LDS_MAX},
+                                      {reinterpret_cast<const void *>(scan_kernel(true, BARK_ACQ_LCB_MEAN, true)), ACQ_LDS_MAX},
+                                      {reinterpret_cast<const void *>(scan_kernel(true, BARK_ACQ_EI, true)), ACQ_LDS_MAX},
+                                      {reinterpret_cast<const void *>(scan_kernel(true, BARK_ACQ_PI, true)), ACQ_LDS_MAX},
+                                      {reinterpret_cast<const void *>(scan_kernel(true, BARK_ACQ_MES, true)), ACQ_LDS_MAX},
                                       {reinterpret_cast<const void *>(acq_condition_kernel), acq_condition_lds_bytes(8192)},
                                       {reinterpret_cast<const void *>(acq_condition_from_kernel), acq_condition_lds_bytes(8192)},
                                       {reinterpret_cast<const void *>(acq_observe_kernel), acq_observe_lds_bytes(8192)}};
@@ -552,28 +578,30 @@ int acq_pack(const double *Minv, const double *w, int R, int bc, double *tab, hi
 
 // variant: 1 LDS, 2 global (resolved by bark_acquisition_plan); n candidates of one slab against the bc forests of the chunk.
 // kind: BARK_ACQ_*; both confidence bounds run the same kernel, the target kinds read targets (bc, S).
+// weights: the chunk's rows of the normalised forest weights (the weighted instantiation), or null (the equal-weight one).
 int acq_scan(int variant, int kind, const uint32_t *ccodes, int W, int cpad, int n, const double *wvec, const double *Minv,
              const double *tab, int R, const double *noise, const double *scale, int m, int bc, double kappa, const double *targets,
-             int S, int first, double *acc, size_t astride, hipStream_t s) {
+             int S, int first, double *acc, size_t astride, const double *weights, hipStream_t s) {
     const dim3 g((unsigned)((n + ACQ_TILE - 1) / ACQ_TILE));
     const int rc = raise_acq_lds_limits();
     if (rc) return rc;
     const bool lds = variant == 1;
     const size_t bytes = scan_lds_bytes(R, m, lds);
-    hipLaunchKernelGGL(scan_kernel(lds, kind), g, dim3(ACQ_TILE), bytes, s, ccodes, W, cpad, n, wvec, Minv, tab, R, noise, scale, m, bc,
-                       kappa, targets, S, first, acc, astride);
+    hipLaunchKernelGGL(scan_kernel(lds, kind, weights != nullptr), g, dim3(ACQ_TILE), bytes, s, ccodes, W, cpad, n, wvec, Minv, tab, R,
+                       noise, scale, m, bc, kappa, targets, S, first, acc, astride, weights);
     BARK_LAUNCH_CHECK();
     return BARK_OK;
 }
 
 int acq_finish(const double *acc, int64_t C, int B, double kappa, int kind, const int64_t *skip, int n_skip, double *acq_out,
-               double *part_v, int64_t *part_i, const int32_t *info, double *best, int64_t *best_i, hipStream_t s) {
+               double *part_v, int64_t *part_i, const int32_t *info, const double *weights, double *best, int64_t *best_i,
+               hipStream_t s) {
     const int nblk = (int)acq_partials(C);
-    hipLaunchKernelGGL(acq_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, s, acc, (long long)C, B, kappa, kind,
+    hipLaunchKernelGGL(acq_finish_kernel, dim3((unsigned)nblk), dim3(256), 0, s, acc, (long long)C, B, weights ? 1 : 0, kappa, kind,
                        reinterpret_cast<const long long *>(skip), n_skip, acq_out, part_v, reinterpret_cast<long long *>(part_i));
     BARK_LAUNCH_CHECK();
     hipLaunchKernelGGL(acq_best_kernel, dim3(1), dim3(256), 0, s, part_v, reinterpret_cast<const long long *>(part_i), nblk, info, B,
-                       best, reinterpret_cast<long long *>(best_i));
+                       weights, best, reinterpret_cast<long long *>(best_i));
     BARK_LAUNCH_CHECK();
     return BARK_OK;
 }

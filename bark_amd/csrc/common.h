@@ -183,12 +183,15 @@ int acq_observe(const uint32_t *pcodes, int W, int ppad, int P, double *Minv, do
 // image of the chunk for the LDS variant
 int acq_pack(const double *Minv, const double *w, int R, int bc, double *tab, hipStream_t s);
 // variant: 1 LDS, 2 global (resolved by bark_acquisition_plan); n candidates of one slab against the bc forests of the chunk;
-// kind: BARK_ACQ_*, the target kinds with the chunk's targets (bc, S)
+// kind: BARK_ACQ_*, the target kinds with the chunk's targets (bc, S); weights: the chunk's rows of the normalised forest
+// weights (every term times its forest's weight, weight 0 skipped), or null for the equal-weight scan
 int acq_scan(int variant, int kind, const uint32_t *ccodes, int W, int cpad, int n, const double *wvec, const double *Minv,
              const double *tab, int R, const double *noise, const double *scale, int m, int bc, double kappa, const double *targets,
-             int S, int first, double *acc, size_t astride, hipStream_t s);
+             int S, int first, double *acc, size_t astride, const double *weights, hipStream_t s);
+// weights (B,) or null as given to acq_scan: with them nothing is divided by B and a forest of weight 0 cannot fail the call
 int acq_finish(const double *acc, int64_t C, int B, double kappa, int kind, const int64_t *skip, int n_skip, double *acq_out,
-               double *part_v, int64_t *part_i, const int32_t *info, double *best, int64_t *best_i, hipStream_t s);
+               double *part_v, int64_t *part_i, const int32_t *info, const double *weights, double *best, int64_t *best_i,
+               hipStream_t s);
 
 // scores.hip (launchers of bark_predictive_scores_hip, leafsystem.hip)
 // n points of one slab, whose first tile is tile0 of the call's `tiles`, against the bc forests of the chunk: the mixture's

@@ -541,14 +541,14 @@ int bark_acquisition_scan_targets_hip(bark_ctx *ctx, const void *packed, const b
             if ((r = sys.walk_candidates(cand + (size_t)s0 * d, n))) return r;
             r = acq_scan(var, lcb ? BARK_ACQ_LCB_MEAN : kind, a.ccodes, sys.W, (int)bark_leaf_npad(n), (int)n, a.w, a.Minv, a.tab, sys.R,
                          noise + c0, scale + c0, sys.m, sys.bc, kappa, lcb ? nullptr : targets + (size_t)c0 * S, lcb ? 0 : (int)S,
-                         c0 == 0, a.acc + s0, (size_t)C, sys.caller);
+                         c0 == 0, a.acc + s0, (size_t)C, nullptr, sys.caller);
             if (r) return r;
         }
         return sys.close_chunk();
     });
     if (rc) return rc;
-    return acq_finish(a.acc, C, (int)sys.B, kappa, kind, skip_idx, (int)n_skip, acq_out, a.part, a.part_i, info_out, best_out, idx_out,
-                      sys.caller);
+    return acq_finish(a.acc, C, (int)sys.B, kappa, kind, skip_idx, (int)n_skip, acq_out, a.part, a.part_i, info_out, nullptr, best_out,
+                      idx_out, sys.caller);
 }
 
 // the confidence bounds only: the two entry points without targets refuse every other kind
@@ -632,13 +632,16 @@ int bark_leaf_posterior_fit_hip(bark_ctx *ctx, const void *packed, const bark_pa
 // The scan of bark_acquisition_scan_targets_hip from its `P > 0` on, with M^-1 and w read from the state.  The state is only
 // read: pending points condition a copy of the chunk's M^-1 in the workspace (acq_condition_from_kernel).  info_out starts
 // as the state's status and takes the faults of this call's walks.
-int bark_acquisition_scan_fitted_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, int64_t d, const double *noise,
-                                     const double *scale, const void *state, size_t state_bytes, const double *cand, int64_t C,
-                                     const double *pending, int64_t P, const int64_t *skip_idx, int64_t n_skip, const double *targets,
-                                     int64_t S, double kappa, int kind, int variant, double *acq_out, double *best_out,
-                                     int64_t *idx_out, int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc,
-                                     void *stream_) {
-    static const char *name = "bark_acquisition_scan_fitted_hip";
+//
+// weights (device, (B,), normalised by the caller) or null: bark_acquisition_scan_fitted_weighted_hip.  The weighted
+// instantiation of the scan and the finish without the division by B; a chunk whose first forests have weight 0 still passes
+// `first`, because the kernel starts its sums at zero whichever forest it skips.  Pending points condition the scratch copy
+// of every forest, whatever its weight: that kernel does not know about weights.
+static int scan_fitted(const char *name, bark_ctx *ctx, const void *packed, const bark_pack_info *info, int64_t d, const double *noise,
+                       const double *scale, const void *state, size_t state_bytes, const double *cand, int64_t C, const double *pending,
+                       int64_t P, const int64_t *skip_idx, int64_t n_skip, const double *targets, int64_t S, double kappa, int kind,
+                       int variant, const double *weights, double *acq_out, double *best_out, int64_t *idx_out, int32_t *info_out,
+                       void *workspace, size_t workspace_bytes, int64_t Bc, void *stream_) {
     error_buffer()[0] = 0;
     if (!info || !cand || !best_out || !idx_out) return fail(BARK_ERR_ARG, "%s: null argument", name);
     if (C < 1 || C > (1 << 24)) return fail(BARK_ERR_ARG, "%s: bad shape C=%lld", name, (long long)C);
@@ -680,13 +683,42 @@ int bark_acquisition_scan_fitted_hip(bark_ctx *ctx, const void *packed, const ba
             if ((rc = walk_one_hot(packed_c, &sub, cand + (size_t)s0 * fc.d, n, fc.d, W, a.ccodes, ctx->fault, fc.caller))) return rc;
             rc = acq_scan(var, lcb ? BARK_ACQ_LCB_MEAN : kind, a.ccodes, W, (int)bark_leaf_npad(n), (int)n, w, Minv, a.tab, R, noise + c0,
                           scale + c0, m, bc, kappa, lcb ? nullptr : targets + (size_t)c0 * S, lcb ? 0 : (int)S, c0 == 0, a.acc + s0,
-                          (size_t)C, fc.caller);
+                          (size_t)C, weights ? weights + c0 : nullptr, fc.caller);
             if (rc) return rc;
         }
         if ((rc = fc.fault_info(info_out + c0, bc))) return rc;
     }
-    return acq_finish(a.acc, C, (int)fc.B, kappa, kind, skip_idx, (int)n_skip, acq_out, a.part, a.part_i, info_out, best_out, idx_out,
-                      fc.caller);
+    return acq_finish(a.acc, C, (int)fc.B, kappa, kind, skip_idx, (int)n_skip, acq_out, a.part, a.part_i, info_out, weights, best_out,
+                      idx_out, fc.caller);
+}
+
+int bark_acquisition_scan_fitted_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, int64_t d, const double *noise,
+                                     const double *scale, const void *state, size_t state_bytes, const double *cand, int64_t C,
+                                     const double *pending, int64_t P, const int64_t *skip_idx, int64_t n_skip, const double *targets,
+                                     int64_t S, double kappa, int kind, int variant, double *acq_out, double *best_out,
+                                     int64_t *idx_out, int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc,
+                                     void *stream_) {
+    return scan_fitted("bark_acquisition_scan_fitted_hip", ctx, packed, info, d, noise, scale, state, state_bytes, cand, C, pending, P,
+                       skip_idx, n_skip, targets, S, kappa, kind, variant, nullptr, acq_out, best_out, idx_out, info_out, workspace,
+                       workspace_bytes, Bc, stream_);
+}
+
+// the weights stay where the caller has them: nothing is added to the workspace
+size_t bark_acquisition_scan_fitted_weighted_workspace_bytes(int64_t max_bits, int64_t m, int64_t Bc, int64_t C, int64_t P,
+                                                             int variant) {
+    return bark_acquisition_scan_fitted_workspace_bytes(max_bits, m, Bc, C, P, variant);
+}
+
+int bark_acquisition_scan_fitted_weighted_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, int64_t d,
+                                              const double *noise, const double *scale, const void *state, size_t state_bytes,
+                                              const double *cand, int64_t C, const double *pending, int64_t P,
+                                              const int64_t *skip_idx, int64_t n_skip, const double *targets, int64_t S, double kappa,
+                                              int kind, int variant, const double *weights, double *acq_out, double *best_out,
+                                              int64_t *idx_out, int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc,
+                                              void *stream_) {
+    return scan_fitted("bark_acquisition_scan_fitted_weighted_hip", ctx, packed, info, d, noise, scale, state, state_bytes, cand, C,
+                       pending, P, skip_idx, n_skip, targets, S, kappa, kind, variant, weights, acq_out, best_out, idx_out, info_out,
+                       workspace, workspace_bytes, Bc, stream_);
 }
 
 // The state conditioned in place on P more points, in the order given (acq_condition_kernel on the state's M^-1; w does not

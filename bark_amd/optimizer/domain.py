@@ -413,12 +413,12 @@ def propose_from_domain(model, data, bounds, feat_types, kappa: float = 1.96, ki
     b, ft = check_bounds(bounds, feat_types)
     if posterior is not None:
         posterior = _fitted(posterior, ft)
-    table = split_table(model[0] if posterior is None else posterior.forest, b, ft)
+    table = split_table(model[0] if posterior is None else posterior.live_forest, b, ft)  # weight-0 forests cut no cell
     plan = domain_plan(table)
     dev = _DeviceTable(table, b, ft)
     repair, counts = None, None
     if constraints is not None:
-        forest = model[0] if posterior is None else posterior.forest
+        forest = model[0] if posterior is None else posterior.live_forest
         boxes = _DeviceBoxes(cell_boxes(forest, b, ft), ft, constraints, passes)
         counts = torch.zeros(2, dtype=torch.int64, device=dev.rep.device)  # rows repaired, rows feasible
 

@@ -31,12 +31,25 @@ def generate_fstar_samples(model, data, domain, num_samples: int = 10, maximise:
 
 # ---- Thompson sampling from the fitted posterior: one sample path per proposal, each minimised on its own ----
 
-def thompson_forests(B: int, q: int, seed: int = 0) -> np.ndarray:
-    """The forest of each of the q draws: uniform over the B forest samples, `numpy.random.default_rng(seed)`.  Host only."""
+def thompson_forests(B: int, q: int, seed: int = 0, weights=None) -> np.ndarray:
+    """The forest of each of the q draws: uniform over the B forest samples, `numpy.random.default_rng(seed)`.  weights: (B,)
+    normalised importance weights of the forests (`LeafPosterior.weights`); the draws are then `rng.choice(B, q, p=weights)`,
+    so a forest of weight 0 is never drawn.  None is the uniform call, the same array as before.  Host only."""
     q = int(q)
     if q < 1:
         raise ValueError(f"q must be positive, got {q}")
-    return np.random.default_rng(seed).integers(0, int(B), size=q).astype(np.int64)
+    rng = np.random.default_rng(seed)
+    if weights is None:
+        return rng.integers(0, int(B), size=q).astype(np.int64)
+    p = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if p.shape[0] != int(B) or not np.isfinite(p).all() or (p < 0).any() or not p.sum() > 0:
+        raise ValueError(f"weights must be ({int(B)},) non-negative finite numbers with a positive sum")
+    return rng.choice(int(B), size=q, p=p / p.sum()).astype(np.int64)
+
+
+def _forest_weights_of(post):
+    """the state's weights on the host for `thompson_forests`, None while it has none"""
+    return None if post.log_weights is None else post.weights.cpu().numpy()
 
 
 def _posterior_of(model, data, domain, posterior):
@@ -50,8 +63,8 @@ def _posterior_of(model, data, domain, posterior):
 
 def propose_thompson_from_candidates(model, data, candidates, domain, q: int, *, seed: int = 0, posterior=None,
                                      return_info: bool = False):
-    """-> indices (q,) int64 into `candidates`: a batch of q Thompson proposals.  Each draw takes a forest sample uniformly
-    (`thompson_forests(B, q, seed)`), one posterior sample path of it (`LeafPosterior.sample_paths(forests=..., seed=seed)`:
+    """-> indices (q,) int64 into `candidates`: a batch of q Thompson proposals.  Each draw takes a forest sample uniformly,
+    or by the state's importance weights when it has them (`thompson_forests(B, q, seed, weights)`), one posterior sample path of it (`LeafPosterior.sample_paths(forests=..., seed=seed)`:
     a repeated forest gets draw numbers 0, 1, ...) and that path's arg-min over the candidates (ties: the lowest index).  No
     outcome is fantasised and the draws do not see each other, so two draws can name the same candidate: duplicates are kept,
     and info["unique"] says how many distinct candidates the batch holds.
@@ -61,7 +74,7 @@ def propose_thompson_from_candidates(model, data, candidates, domain, q: int, *,
     pending points.  numpy candidates give a numpy array, torch candidates a device tensor.  With return_info: (indices, info),
     info = {"forest", "draw", "value" (one per draw, numpy), "unique"}."""
     post = _posterior_of(model, data, domain, posterior)
-    forests = thompson_forests(post.B, q, seed)
+    forests = thompson_forests(post.B, q, seed, _forest_weights_of(post))
     paths = post.sample_paths(forests=forests, seed=seed)
     values, index = paths.minimise(candidates)
     if not return_info:
@@ -103,7 +116,7 @@ def propose_thompson_from_domain(model, data, bounds, feat_types, q: int, *, see
         raise ValueError(f"unknown mode {mode!r} (use 'cells' or 'uniform')")
     b, ft = check_bounds(bounds, feat_types)
     post = _posterior_of(model, data, ft, posterior)
-    forests = thompson_forests(post.B, q, seed)
+    forests = thompson_forests(post.B, q, seed, _forest_weights_of(post))
     paths = post.sample_paths(forests=forests, seed=seed)
     X = np.full((int(q), post.d), np.nan)
     info = [None] * int(q)

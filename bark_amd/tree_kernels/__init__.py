@@ -1,4 +1,5 @@
-from .posterior import LeafPaths, LeafPosterior, fit_posterior, path_list, paths_plan  # noqa: F401
+from .posterior import (LeafPaths, LeafPosterior, fit_posterior, forest_weights, path_list, paths_plan,  # noqa: F401
+                        systematic_index)
 from .scores import loo_scores, predictive_scores  # noqa: F401
 from .tree_gps import (  # noqa: F401
     BARKModel,

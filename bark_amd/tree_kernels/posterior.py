@@ -7,6 +7,13 @@ result; its `scan` is the same scan from that state (bark_acquisition_scan_fitte
 batch takes between two picks (bark_leaf_posterior_condition_hip), and `observe` / `fantasise` / `log_predictive` move the
 state forward on points with observed or sampled values (bark_leaf_posterior_observe_hip).  include/bark_hip.h has the contract: a scan from the
 state returns the bits of the stateless scan that uses the `chunk` the state was fitted with.
+
+The B forests are a sample of the tree posterior given the data of the fit.  After `observe_` they are a sample of the OLD
+posterior; the exact correction is one importance weight per forest, w_b <- w_b p_b(y_new | data), and p_b is the log
+predictive the observe kernel computes anyway.  `log_weights` holds them (None: equal weights, and then nothing changes a
+bit): `observe_(reweight=True)` / `reweight_` update them (bark_forest_weights_hip), `ess` says how many forests still
+matter, `resample` / `subset` thin them (bark_leaf_posterior_gather_hip), and `scan` (bark_acquisition_scan_fitted_weighted_hip)
+and the Thompson proposals honour them — fit, propose, observe, propose as a sequential Monte Carlo loop.
 """
 
 from __future__ import annotations
@@ -17,7 +24,7 @@ import numpy as np
 
 from .. import _lib
 from ..fitting.mll import _feat_types_of, _fit_chunk, _forest3, _leaf_call, _leaf_inputs, _raise_on_info
-from ..forest import _is_torch, _points
+from ..forest import _is_torch, _points, packed_forest
 
 MAX_TREES, MAX_LEAVES = 64, 8192  # limits of the leaf-space posterior (include/bark_hip.h)
 MAX_PENDING = 64  # points per call of `condition`, and pending points of a scan
@@ -33,7 +40,9 @@ class LeafPosterior:
     forest records on the host (`forest`, for `propose_from_domain`'s cell table), `noise` and `scale` (device, (B,)),
     `feat_types`, and B, m, R, d, N.  `info` is the device int32 status per forest (a view of the state; all zero unless a
     later `condition_` met an invalid categorical value), `train_y_min` the default target of kind "ei" / "pi", `chunk` the
-    forests per chunk it was fitted with.  Made by `fit_posterior`; there is no CPU fallback."""
+    forests per chunk it was fitted with.  `log_weights`: None (equal weights) or the forests' log importance weights, a
+    device float64 (B,) tensor whose log-sum-exp is 0, -inf for a dead forest; treat the tensor as read-only (copies share
+    it).  `log_normaliser`: what the last `reweight_` returned.  Made by `fit_posterior`; there is no CPU fallback."""
 
     def __init__(self, q, state, chunk):
         self.packed, self.forest, self.feat_types = q.pf, q.nodes3, q.ft
@@ -41,6 +50,29 @@ class LeafPosterior:
         self.B, self.m, self.R, self.d, self.N = q.B, q.m, q.R, q.d, q.N
         self.state, self.chunk = state, chunk
         self.train_y_min = float(q.yd.min())
+        self.log_weights, self.log_normaliser = None, None
+
+    @property
+    def weights(self):
+        """(B,) device float64: the normalised weights exp(log_weights), all 1 / B while there are none"""
+        import torch
+
+        if self.log_weights is None:
+            return torch.full((self.B,), 1.0 / self.B, dtype=torch.float64, device=self.state.device)
+        return torch.exp(self.log_weights)
+
+    @property
+    def ess(self) -> float:
+        """the effective sample size 1 / sum_b w_b^2: B for equal weights, 1 when one forest holds all the weight"""
+        w = self.weights
+        return float(1.0 / (w * w).sum().item())
+
+    @property
+    def live_forest(self):
+        """the records of the forests whose weight is not zero, in forest order (all of them while there are no weights)"""
+        if self.log_weights is None:
+            return self.forest
+        return self.forest[(self.weights > 0).cpu().numpy()]
 
     @property
     def nbytes(self) -> int:
@@ -59,8 +91,9 @@ class LeafPosterior:
         new.state = self.state.clone()
         return new
 
-    def _call(self, fn, need, chunk, *args):
-        """Run an entry point that starts from the state: args stand between `scale` and `info_out`."""
+    def _call(self, fn, need, chunk, *args, weights=None):
+        """Run an entry point that starts from the state: args stand between `scale` and `info_out`.  weights: the device
+        weights of a weighted scan; the status of a forest of weight 0 raises nothing, as it fails nothing in the call."""
         import torch
 
         info = torch.empty(self.B, dtype=torch.int32, device=self.state.device)
@@ -68,14 +101,36 @@ class LeafPosterior:
         ws = _lib.workspace(need(Bc))
         _lib.check(fn(_lib.ctx(), _lib.ptr(self.packed.packed), self.packed.info_ref, self.d, _lib.ptr(self.noise), _lib.ptr(self.scale),
                       *args, _lib.ptr(info), _lib.ptr(ws), ws.numel(), Bc, _lib.stream_ptr()))
-        _raise_on_info(info, "leaf-space system")
+        _raise_on_info(info if weights is None else torch.where(weights == 0, torch.zeros_like(info), info), "leaf-space system")
+
+    def _scan_weights(self, weights):
+        """`scan`'s weights=, checked on the host -> None (the equal-weight call), the state's device weights or a normalised
+        host array (B,)"""
+        if weights is None:
+            return None
+        if isinstance(weights, str):
+            if weights != "state":
+                raise ValueError(f"weights must be 'state', None or a ({self.B},) array, got {weights!r}")
+            return None if self.log_weights is None else self.weights
+        w = np.asarray(weights.detach().cpu() if _is_torch(weights) else weights, dtype=np.float64)
+        if w.shape != (self.B,):
+            raise ValueError(f"weights must be ({self.B},), got {w.shape}")
+        if not np.isfinite(w).all() or (w < 0).any() or not w.sum() > 0:
+            raise ValueError("weights must be non-negative finite numbers with a positive sum")
+        return w / w.sum()
 
     def scan(self, candidates, kappa: float = 1.96, kind: str = "lcb_mean", return_values: bool = False, chunk: int | None = None,
-             variant: str = "auto", pending=None, skip=None, targets=None):
+             variant: str = "auto", pending=None, skip=None, targets=None, weights="state"):
         """What `acquisition_scan(model, data, candidates, domain, ...)` returns, by the same numpy / torch conventions and
         with the same errors, from the state: nothing of size N is touched.  The state is not modified; pending points
         condition a scratch copy of M^-1 inside the call.  Bit for bit the stateless result at the `chunk` of the fit; the
-        `chunk` given here only bounds this call's workspace."""
+        `chunk` given here only bounds this call's workspace.
+
+        weights: "state" (the default) averages the forests with the state's importance weights when it has them
+        (`log_weights`), and is the call above when it has none; None forces equal weights; a (B,) array of non-negative
+        finite numbers with a positive sum is normalised on the host and used for this call only.  With weights every
+        per-forest term is multiplied by its forest's weight instead of 1 / B — `lcb_mixture` gets the weighted moments — and
+        a forest of weight exactly 0 is skipped whole: its status fails nothing.  Pending points condition every forest."""
         from ..optimizer.acquisition import KINDS, TARGET_KINDS, VARIANTS, _skip_indices, _target_matrix, acquisition_plan
 
         if kind not in KINDS:
@@ -88,6 +143,7 @@ class LeafPosterior:
         if len(candidates) < 1:
             raise ValueError("acquisition scan needs at least one candidate")
         tgt = _target_matrix(targets, self.B, kind, np.array([self.train_y_min])) if kind in TARGET_KINDS else None
+        w_d = self._scan_weights(weights)
 
         import torch
 
@@ -100,15 +156,23 @@ class LeafPosterior:
             raise ValueError(f"acquisition scan supports at most {MAX_PENDING} pending points (got {P})")
         skip_d = None if skip is None else _skip_indices(skip, C)
         tgt_d = None if tgt is None else _lib.to_device(tgt, torch.float64)
+        w_d = None if w_d is None else _lib.to_device(w_d, torch.float64)
         acq = torch.empty(C, dtype=torch.float64, device=dev) if return_values else None
         best = torch.empty((), dtype=torch.float64, device=dev)
         idx = torch.empty((), dtype=torch.int64, device=dev)
         lib = _lib.lib()
-        self._call(lib.bark_acquisition_scan_fitted_hip,
-                   lambda k: int(lib.bark_acquisition_scan_fitted_workspace_bytes(R, self.m, k, C, P, VARIANTS[variant])), chunk,
-                   _lib.ptr(self.state), self.nbytes, _lib.ptr(cand_d), C, _lib.ptr(pend_d), P, _lib.ptr(skip_d),
-                   0 if skip_d is None else int(skip_d.numel()), _lib.ptr(tgt_d), 0 if tgt_d is None else int(tgt_d.shape[1]), kappa,
-                   KINDS[kind], VARIANTS[variant], _lib.ptr(acq), _lib.ptr(best), _lib.ptr(idx))
+        front = (_lib.ptr(self.state), self.nbytes, _lib.ptr(cand_d), C, _lib.ptr(pend_d), P, _lib.ptr(skip_d),
+                 0 if skip_d is None else int(skip_d.numel()), _lib.ptr(tgt_d), 0 if tgt_d is None else int(tgt_d.shape[1]), kappa,
+                 KINDS[kind], VARIANTS[variant])
+        outs = (_lib.ptr(acq), _lib.ptr(best), _lib.ptr(idx))
+        if w_d is None:
+            self._call(lib.bark_acquisition_scan_fitted_hip,
+                       lambda k: int(lib.bark_acquisition_scan_fitted_workspace_bytes(R, self.m, k, C, P, VARIANTS[variant])), chunk,
+                       *front, *outs)
+        else:
+            self._call(lib.bark_acquisition_scan_fitted_weighted_hip,
+                       lambda k: int(lib.bark_acquisition_scan_fitted_weighted_workspace_bytes(R, self.m, k, C, P, VARIANTS[variant])),
+                       chunk, *front, _lib.ptr(w_d), *outs, weights=w_d)
         if _is_torch(candidates):
             return (best, idx, acq) if return_values else (best, idx)
         out = (float(best.item()), int(idx.item()))
@@ -176,29 +240,119 @@ class LeafPosterior:
                    _lib.ptr(eps_d), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), int(draw), _lib.ptr(self.state), self.nbytes,
                    _lib.ptr(values_out), _lib.ptr(logpred_out))
 
-    def observe_(self, points, values, chunk: int | None = None) -> "LeafPosterior":
+    def observe_(self, points, values, chunk: int | None = None, reweight: bool = False) -> "LeafPosterior":
         """Take in real observations: the state becomes, to rounding, what `fit_posterior` gives on the data plus
         (`points`, `values`), by one rank-one step per point and forest on M^-1 and w instead of a refit
         (bark_leaf_posterior_observe_hip).  values: (P,) or (P, 1), finite, else ValueError.  More than 64 points are applied
         in slices of 64, in order.  Sets N += P and train_y_min = min(train_y_min, values.min()); everything that reads the
         state (`scan`, `sample_paths`, the `propose_*` functions) follows.  Returns self.  After a ValueError for an invalid
         categorical value the state is marked failed (`info` = -1).  chunk: forests per launch; it bounds the workspace and
-        changes no bit, here and in `fantasise` and `log_predictive`."""
+        changes no bit, here and in `fantasise` and `log_predictive`.
+
+        reweight=True also multiplies every forest's importance weight by its predictive density of the new values: the
+        observe calls that update the state write each forest's log predictive (what `log_predictive` returns for the state
+        before the update, by the same kernel, slices and sums — no second pass over the state), and the sum goes through
+        `reweight_`; `log_normaliser` then holds the log predictive density of the weighted mixture.  A forest that could
+        not have produced the data fades out, and `ess` says when to `resample` or to rerun the sampler.  ValueError when
+        no forest is left with a weight: state and weights are then put back as they were.  That promise costs a copy of
+        the state before the update (one device copy of 8 B R^2 bytes, and as much memory until the call returns); the
+        update itself still reads and writes the state once.  The default changes nothing and copies nothing."""
+        import torch
+
         if points is None or len(points) == 0:
             return self
         pend_d = _points(points, self.d)[0]
         P = int(pend_d.shape[0])
         v = self._values(values, P, forests=False)
+        if reweight:
+            backup = self.state.clone()
+            total = torch.zeros(self.B, dtype=torch.float64, device=self.state.device)
+            part = torch.empty_like(total)
         for p0 in range(0, P, MAX_PENDING):
-            self._observe(pend_d[p0:p0 + MAX_PENDING], v[p0:p0 + MAX_PENDING], chunk=chunk)
+            self._observe(pend_d[p0:p0 + MAX_PENDING], v[p0:p0 + MAX_PENDING], chunk=chunk, logpred_out=part if reweight else None)
+            if reweight:
+                total += part
+        if reweight:
+            try:
+                self.reweight_(total)
+            except ValueError:
+                self.state.copy_(backup)
+                raise
         self.N += P
         self.train_y_min = min(self.train_y_min, float(v.min()))
         return self
 
-    def observe(self, points, values, chunk: int | None = None) -> "LeafPosterior":
+    def observe(self, points, values, chunk: int | None = None, reweight: bool = False) -> "LeafPosterior":
         """A new LeafPosterior that has taken in the observations (`observe_`): it shares the forests and owns a copy of the
         state."""
-        return self._copy().observe_(points, values, chunk)
+        return self._copy().observe_(points, values, chunk, reweight)
+
+    def reweight_(self, log_increment) -> float:
+        """Multiply the forests' weights by exp(log_increment) ((B,), numpy or torch) and renormalise them on the device
+        (bark_forest_weights_hip) -> the log normaliser log sum_b w_b exp(inc_b); for a predictive increment that is the log
+        predictive density of the weighted mixture.  -inf kills a forest, and so does a non-zero status of the state.
+        ValueError, with the weights as they were, for a wrong shape, NaN or +inf in the increment, or when no forest would be
+        left with a weight."""
+        import torch
+
+        inc = log_increment.detach() if _is_torch(log_increment) else torch.from_numpy(np.asarray(log_increment, dtype=np.float64))
+        if tuple(inc.shape) != (self.B,):
+            raise ValueError(f"log_increment must be ({self.B},), got {tuple(inc.shape)}")
+        if bool((torch.isnan(inc) | (inc == math.inf)).any()):
+            raise ValueError("log_increment must not hold NaN or +inf")
+        inc = _lib.to_device(inc, torch.float64)
+        log_w, _, stats = forest_weights(self.log_weights, inc, self.info)
+        if stats[0] == -math.inf:
+            raise ValueError("no forest is left with a non-zero weight: the forest samples cannot explain the data (rerun the sampler)")
+        self.log_weights, self.log_normaliser = log_w, float(stats[0])
+        return self.log_normaliser
+
+    def subset(self, index) -> "LeafPosterior":
+        """A new LeafPosterior of the n >= 1 forests `index` (ints in [0, B), repeats and any order allowed): their rows of
+        the state copied on the device (bark_leaf_posterior_gather_hip), `noise` and `scale` gathered there, the records
+        indexed on the host and packed again.  `log_weights` are gathered and renormalised; None stays None.  ValueError for
+        an index out of range or when every chosen forest has weight 0."""
+        import torch
+
+        idx = np.asarray(index)
+        if idx.ndim != 1 or idx.shape[0] < 1 or not np.issubdtype(idx.dtype, np.integer):
+            raise ValueError("index must be a non-empty 1-d array of ints")
+        if idx.min() < 0 or idx.max() >= self.B:
+            raise ValueError(f"index must lie in [0, {self.B})")
+        idx = idx.astype(np.int64)
+        n = int(idx.shape[0])
+        idx_d = _lib.to_device(idx)
+        lib = _lib.lib()
+        nbytes = int(lib.bark_leaf_posterior_bytes(self.R, self.m, n))
+        if nbytes == 0:
+            raise ValueError(f"a fitted posterior refuses the shape B = {n}, m = {self.m}, R = {self.R}")
+        log_w = None
+        if self.log_weights is not None:
+            # decided on the host, before anything is launched: the (B,) log weights are read back once
+            if not np.isfinite(self.log_weights.cpu().numpy()[idx]).any():
+                raise ValueError("every forest of the subset has weight 0")
+            log_w = forest_weights(self.log_weights[idx_d], None, None)[0]
+        state = torch.empty(nbytes, dtype=torch.uint8, device=self.state.device)
+        _lib.check(lib.bark_leaf_posterior_gather_hip(_lib.ptr(self.state), self.B, self.R, _lib.ptr(idx_d), n, _lib.ptr(state),
+                                                      _lib.stream_ptr()))
+        new = object.__new__(LeafPosterior)
+        new.__dict__.update(self.__dict__)
+        new.state, new.B, new.chunk, new.log_weights = state, n, min(self.chunk, n), log_w
+        new.log_normaliser = None  # it described a reweighting of the source's sample
+        new.noise, new.scale = self.noise[idx_d].contiguous(), self.scale[idx_d].contiguous()
+        new.forest = np.ascontiguousarray(self.forest[idx])
+        new.packed = _PackedAs(packed_forest(new.forest, self.feat_types), self.R)
+        return new
+
+    def resample(self, n: int | None = None, seed: int = 0) -> "LeafPosterior":
+        """Systematic resampling -> a new LeafPosterior of n (default B) equally weighted forests (`log_weights` None): forest b
+        occurs floor(n w_b) or ceil(n w_b) times, a forest of weight 0 never.  The index is host work
+        (`systematic_index(weights, n, seed)`: one uniform from `numpy.random.default_rng(seed)`), the copy is `subset`.
+        Duplicates are exact copies; nothing rejuvenates them."""
+        n = self.B if n is None else int(n)
+        new = self.subset(systematic_index(self.weights.cpu().numpy(), n, seed))
+        new.log_weights = None
+        return new
 
     def fantasise(self, points, seed: int = 0, draw: int = 0, eps=None, chunk: int | None = None):
         """-> (LeafPosterior, values (B, P)): a copy conditioned on `points` (P <= 64) at values drawn from each forest's own
@@ -328,6 +482,65 @@ def fit_posterior(model, data, domain, chunk: int | None = None) -> LeafPosterio
     Bc = int(chunk) if chunk else _fit_chunk(q.B, need)
     _leaf_call(q, lib.bark_leaf_posterior_fit_hip, need, Bc, _lib.ptr(state), nbytes)
     return LeafPosterior(q, state, Bc)
+
+
+class _PackedAs:
+    """A PackedForest presented with the leaf-space width R of the state it belongs to: a subset's own forests may have
+    fewer leaves than the widest forest of the fit, and the state keeps R columns per forest.  The pack is shared (it may sit
+    in the pack cache); only the copy of its info says R."""
+
+    def __init__(self, pf, R: int):
+        import ctypes
+
+        self.packed, self.B, self.m, self.L = pf.packed, pf.B, pf.m, pf.L
+        self.info = _lib.PackInfo()
+        ctypes.pointer(self.info)[0] = pf.info
+        if int(pf.info.max_bits) > R:
+            raise ValueError("the forests have more leaves than the state has columns")
+        self.info.max_bits = R
+
+    @property
+    def info_ref(self):
+        import ctypes
+
+        return ctypes.byref(self.info)
+
+
+def forest_weights(log_weights, increment, info=None):
+    """bark_forest_weights_hip -> (log_w (B,), w (B,), stats (3,) numpy): the weights exp(log_weights + increment)
+    normalised on the device, in log form and plain, and {log normaliser, effective sample size, largest weight}.  Either
+    input may be None (zeros); info: device int32 status per forest, non-zero kills the forest.  All dead: stats[0] = -inf
+    and NaN everywhere else.  Reproducible bit for bit from run to run."""
+    import torch
+
+    given = [t for t in (log_weights, increment, info) if t is not None]
+    if not given:
+        raise ValueError("forest_weights needs log_weights, increment or info")
+    B, dev = int(given[0].shape[0]), given[0].device
+    log_w = torch.empty(B, dtype=torch.float64, device=dev)
+    w = torch.empty_like(log_w)
+    stats = torch.empty(3, dtype=torch.float64, device=dev)
+    args = [None if t is None else t.contiguous() for t in (log_weights, increment, info)]
+    _lib.check(_lib.lib().bark_forest_weights_hip(*(_lib.ptr(t) for t in args), B, _lib.ptr(log_w), _lib.ptr(w), _lib.ptr(stats),
+                                                  _lib.stream_ptr()))
+    return log_w, w, stats.cpu().numpy()
+
+
+def systematic_index(weights, n: int, seed: int = 0) -> np.ndarray:
+    """Systematic resampling, host only -> (n,) int64 forest indices, non-decreasing.  One uniform u from
+    `numpy.random.default_rng(seed)`; the positions (u + i) / n, i < n, are looked up in the running sum of `weights` taken in
+    forest order and divided by its last entry: position p names the first forest whose running sum exceeds p, so a forest of
+    weight 0 is never named and forest b is named floor(n w_b) or ceil(n w_b) times."""
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"n must be positive, got {n}")
+    if not np.isfinite(w).all() or (w < 0).any() or not w.sum() > 0:
+        raise ValueError("weights must be non-negative finite numbers with a positive sum")
+    cum = np.cumsum(w)
+    cum /= cum[-1]
+    pos = (np.random.default_rng(seed).random() + np.arange(n)) / n
+    return np.searchsorted(cum, pos, side="right").astype(np.int64)
 
 
 MAX_PATHS_PER_CALL = 4096  # paths per call of the two path entry points (include/bark_hip.h)

@@ -507,6 +507,39 @@ int bark_acquisition_scan_targets_hip(bark_ctx *ctx, const void *packed, const b
  *   workspace >= bark_leaf_posterior_observe_workspace_bytes(R, m, Bc, P): the codes of the points.
  *   Refused with BARK_ERR_ARG before any launch, beside the limits below: points == NULL with P > 0, an unknown mode,
  *   BARK_OBSERVE_VALUES without values, a value_stride other than 0 or P.
+ * Weighted forest samples.  After an observation the B forests are still a sample of the OLD tree posterior; the exact
+ * correction is one importance weight per forest, w_b <- w_b p_b(y_new | data), with p_b the predictive density that
+ * bark_leaf_posterior_observe_hip writes into logpred_out while it updates the state.  Three entry points make the state a
+ * weighted sample; none of them changes a result of the entry points above.
+ * bark_forest_weights_hip: l_b = log_w_in[b] + increment[b] (a NULL array counts as zeros), M = max_b l_b,
+ *   S = sum_b exp(l_b - M), log_w_out[b] = l_b - M - log S, w_out[b] = exp(log_w_out[b]) and
+ *   stats_out = { M + log S, 1 / sum_b w_out[b]^2, max_b w_out[b] }: the log normaliser (for a predictive increment the log
+ *   predictive density of the weighted mixture, when log_w_in is normalised), the effective sample size, the largest weight.
+ *   A forest is dead — l_b = -inf, log_w_out[b] = -inf, w_out[b] = 0 — when info[b] != 0 (info (B,) int32 or NULL), when its
+ *   increment is not finite or when its log_w_in is not finite (-inf: dead before).  If no forest is alive stats_out[0] is
+ *   -inf and every other output is NaN; the caller keeps its old weights.  One workgroup of 256 threads: thread t folds the
+ *   forests t, t + 256, ... in that order, the 256 values meet in a xor butterfly per wave and one LDS stage of four.  The
+ *   order depends on B alone, so two runs give the same bits.  No atomics.  All arrays device, fp64 except info; the outputs
+ *   must not overlap the inputs.  1 <= B <= 2^24.  No workspace.
+ * bark_acquisition_scan_fitted_weighted_hip: bark_acquisition_scan_fitted_hip with `weights` (device, (B,), non-negative, summing to 1:
+ *   the caller normalises).  Every per-forest term of the scan is multiplied by weights[b] before it is added — the three
+ *   sums of the confidence bounds, so kind 1 gets the weighted moments mu = sum_b w_b mu_b, var = sum_b w_b (var_b + mu_b^2)
+ *   - mu^2, and the one sum of the target kinds — and the finish does not divide by B.  A forest whose weight is exactly 0.0 is
+ *   skipped whole by the scan (no table, no leaf lists, no arithmetic) and its status is ignored: info_out still reports it,
+ *   but only a failed forest of non-zero weight makes best_out / idx_out NaN / -1.  With one weight 1.0 and the others 0.0 the
+ *   result has the bits of the plain scan of that forest alone (1.0 t and 0.0 + t are exact, nothing is divided).  Pending
+ *   points condition the scratch copy of every forest whatever its weight; skip_idx, targets, variant and Bc behave as above,
+ *   and the result does not depend on Bc.  weights == NULL is bark_acquisition_scan_fitted_hip itself, bit for bit: the
+ *   equal-weight kernels run.  The weights are not read back: a negative or NaN weight gives a meaningless result and no
+ *   status.  The workspace is that of the unweighted call.
+ * bark_leaf_posterior_gather_hip: state_out (layout of bark_leaf_posterior_bytes(R, m, n)) row k = state_in row index[k], for
+ *   M^-1 (R^2 doubles), w (R doubles) and the status word, k < n; repeats and any order allowed.  index: DEVICE int64 (n,).
+ *   The entry copies it to the host and refuses an entry outside [0, B_in) before the kernel is launched, so the call
+ *   synchronises the stream once.  Loads and stores are 16 bytes wide where both row bases are 16-byte aligned, with the last
+ *   element alone when R^2 is odd, and 8 bytes wide otherwise (R odd puts every other matrix 8 bytes off).  Refused with
+ *   BARK_ERR_ARG: a null pointer, R outside 1 .. 8192, n outside 1 .. 65535, a state that is not 256-byte aligned, and
+ *   state_in / state_out that overlap anywhere in their bark_leaf_posterior_bytes extents.  noise, scale, the packed forests
+ *   and the weights are the caller's to gather.
  * Limits, refused with BARK_ERR_ARG before any launch: those of bark_acquisition_scan_targets_hip; a state buffer smaller
  * than bark_leaf_posterior_bytes or not 256-byte aligned.  The calls only enqueue; the queries are pure host code.
  * ------------------------------------------------------------------------------------- */
@@ -539,6 +572,23 @@ int bark_leaf_posterior_observe_hip(bark_ctx *ctx, const void *packed, const bar
                                     size_t state_bytes, double *values_out /* (B, P) or NULL */,
                                     double *logpred_out /* (B,) or NULL */, int32_t *info_out /* (B,) */, void *workspace,
                                     size_t workspace_bytes, int64_t Bc, void *stream);
+
+int bark_forest_weights_hip(const double *log_w_in /* (B,) or NULL */, const double *increment /* (B,) or NULL */,
+                            const int32_t *info /* (B,) or NULL */, int64_t B, double *log_w_out /* (B,) */, double *w_out /* (B,) */,
+                            double *stats_out /* 3 */, void *stream);
+size_t bark_acquisition_scan_fitted_weighted_workspace_bytes(int64_t max_bits, int64_t m, int64_t Bc, int64_t C, int64_t P,
+                                                             int variant);
+int bark_acquisition_scan_fitted_weighted_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, int64_t d,
+                                              const double *noise, const double *scale, const void *state, size_t state_bytes,
+                                              const double *cand, int64_t C, const double *pending /* (P, d) or NULL */, int64_t P,
+                                              const int64_t *skip_idx /* (n_skip,) or NULL */, int64_t n_skip,
+                                              const double *targets /* (B, S) or NULL for kinds 0 / 1 */, int64_t S, double kappa,
+                                              int kind, int variant, const double *weights /* (B,) or NULL */,
+                                              double *acq_out /* (C,) or NULL */, double *best_out /* 1 */, int64_t *idx_out /* 1 */,
+                                              int32_t *info_out /* (B,) */, void *workspace, size_t workspace_bytes, int64_t Bc,
+                                              void *stream);
+int bark_leaf_posterior_gather_hip(const void *state_in, int64_t B_in, int64_t R, const int64_t *index /* device (n,) */, int64_t n,
+                                   void *state_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------
  * Sample paths from a fitted posterior (Thompson sampling).  A tree kernel has finite rank, so a posterior draw of forest b
