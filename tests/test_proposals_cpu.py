@@ -1,6 +1,7 @@
 """CPU tests of the tree proposals: the host restatement (tests/proposals_ref.py) against the reference's own functions
 (tests/golden/g12_tree_proposals), the Philox stream against the published known answers, the statuses, the library's limit
-checks (pure host) and the noise / scale proposal of bark_amd.fitting.noise_scale_proposals.  No GPU."""
+checks (pure host), the noise / scale proposal of bark_amd.fitting.noise_scale_proposals, and the conditions under which the
+edge cases of tests/test_gpu_proposals_edges.py mean something (restatement only).  No GPU."""
 import ctypes
 import types
 
@@ -221,3 +222,213 @@ def test_params_and_exports():
     assert [e.value for e in fit.TreeProposalEnum] == [0, 1, 2] and [e.name for e in fit.TreeProposalEnum] == ["Grow", "Prune", "Change"]
     for name in ("run_bark_sampler", "propose_trees", "tree_proposals_plan", "noise_scale_proposals"):
         assert hasattr(fit, name)
+
+
+# -------------------------------------------------------------------------------- edge cases ----
+# The conditions that make tests/test_gpu_proposals_edges.py meaningful, asserted on the restatement's outputs alone: a badly
+# chosen seed fails here, not silently on the device.
+MOSTLY_REJECTED = ("idle_short", "tiny", "max_leaves_127", "ladders_stop")     # cases that are about a status other than 0
+
+
+def _edge(name):
+    forests, (new, lq, lu, detail, sa) = pr.edge_ref(name)
+    c = pr.EDGE_CASES[name]
+    return c, forests.reshape(-1, c.L), new.reshape(-1, c.L), detail.reshape(-1, 4), lq.reshape(-1)
+
+
+def _words(nodes):
+    return {int(n) // 64 for n in nodes if n >= 0}
+
+
+def _interval(c, tree, d):
+    return [float(v) for v in pr.subspace(tree, int(d[1]), c.bounds, c.ft)[int(d[2])]]
+
+
+@pytest.mark.parametrize("name", sorted(pr.EDGE_CASES))
+def test_edge_trees_are_trees_with_stale_slots_and_mostly_valid_proposals(name):
+    c, trees, new, detail, lq = _edge(name)
+    assert trees.shape[0] == c.nc * c.m <= 128
+    for k, tree in enumerate(trees):
+        if name == "guarded":
+            assert pr.valid_tree(tree) == (k % c.m == c.m - 1)  # the last tree of every chain is a plain one
+        elif name == "idle_pairs_odd":
+            rest = tree.copy()
+            rest["active"][pr.ORPHANS[k % c.m]] = 0
+            assert not pr.valid_tree(tree) and pr.valid_tree(rest)
+        else:
+            assert pr.valid_tree(tree), (name, k)
+        idle = tree[tree["active"] == 0]
+        assert (idle["is_leaf"] <= 1).all() and all((idle[f] <= c.L).all() for f in ("left", "right", "parent"))
+        if len(idle) >= 2:
+            assert idle["depth"].any() and idle["feature_idx"].any()  # stale bits for the copy to keep
+    # a rejected proposal copies the container unchanged; a grow or a prune changes it
+    for tree, nt, d, q in zip(trees, new, detail, lq):
+        assert (d[3] == 0) == np.isfinite(q)
+        if d[3] != 0 or d[0] != pr.CHANGE:
+            assert (nt.tobytes() == tree.tobytes()) == (d[3] != 0)
+    share = float((detail[:, 3] != 0).mean())
+    print(name, "statuses", np.bincount(detail[:, 3], minlength=5).tolist(), "share of status != 0: %.3f" % share)
+    if not name.startswith(MOSTLY_REJECTED):
+        assert share <= 0.5
+
+
+def test_edge_cases_end_in_ragged_workgroups():
+    assert sum((c.nc * c.m) % 4 != 0 for c in pr.EDGE_CASES.values()) >= 2  # four proposals per workgroup
+
+
+def test_relabel_and_place():
+    rng = np.random.default_rng(8)
+    evolved = pr.evolved_forests(2, 3, 40, pr.MIXED_BOUNDS, pr.MIXED_FT, pr.Params(max_leaves=8), seed=3, sweeps=10).reshape(-1, 40)
+    assert ((evolved["active"] == 0) & (evolved["depth"] > 0)).any()  # pruned records are there
+    for tree in evolved:
+        assert pr.valid_tree(tree)
+        perm = np.concatenate([[0], 1 + rng.permutation(39)])
+        moved = pr.relabel(tree, perm)
+        assert pr.valid_tree(moved) and not pr.valid_tree(pr.relabel(tree, perm)[::-1])
+        idle = np.flatnonzero(tree["active"] == 0)
+        assert moved[perm[idle]].tobytes() == tree[idle].tobytes()                        # inactive records move unchanged
+        assert pr.relabel(moved, np.argsort(perm)).tobytes() == tree.tobytes()
+        assert sorted(pr.terminal(moved)) == sorted(perm[pr.terminal(tree)].tolist())
+        assert sorted(pr.singly_internal(moved)) == sorted(perm[pr.singly_internal(tree)].tolist())
+        n = int(tree["active"].sum())
+        want = sorted(rng.choice(np.arange(1, 256), size=256 - n, replace=False).tolist())
+        put = pr.place(tree, 256, want, rng)
+        assert np.flatnonzero(put["active"] == 0).tolist() == want and pr.valid_tree(put)
+        assert sorted(put["depth"][put["active"] == 1].tolist()) == sorted(tree["depth"][tree["active"] == 1].tolist())
+    with pytest.raises(AssertionError):
+        pr.place(pr.root_tree(8), 8, [1, 2, 3])  # 5 slots for one node
+    # the cases' own inactive sets
+    for name, sets in (("idle_pairs_255", pr.IDLE_PAIRS[255]), ("idle_pairs_256", pr.IDLE_PAIRS[256]), ("idle_short_one", [(200,)] * 3),
+                       ("idle_short_none", [()] * 3), ("idle_pairs_odd", pr.IDLE_PAIRS_ODD)):
+        c, trees, _, _, _ = _edge(name)
+        for k, tree in enumerate(trees):
+            assert np.flatnonzero(tree["active"] == 0).tolist() == list(sets[k % c.m]), (name, k)
+    for name in pr.EDGE_CASES:
+        if name.startswith("spread"):
+            c, trees, _, _, _ = _edge(name)
+            assert ((trees["active"] == 0).sum(axis=1) == (2 if c.L % 2 else 3)).all()
+            assert len({t.tobytes() for t in trees}) == len(trees)
+
+
+def test_caterpillar_has_one_singly_internal_node_where_asked():
+    for L, depth, slot in ((65, 2, 64), (256, 60, 255), (70, 12, None), (3, 1, None)):
+        t = pr.caterpillar(L, depth, 0, 0.5, [j % 2 for j in range(depth)], single_slot=slot)
+        assert pr.valid_tree(t) and len(pr.terminal(t)) == depth + 1 and int(t["depth"].max()) == depth
+        assert pr.singly_internal(t) == [2 * depth - 3 + (depth % 2) if slot is None and depth > 1 else (slot or 0)]
+
+
+def test_spread256_reaches_every_word_with_every_kind():
+    c, trees, new, detail, _ = _edge("spread256")
+    ok = detail[detail[:, 3] == 0]
+    assert set(ok[:, 0].tolist()) == {pr.GROW, pr.PRUNE, pr.CHANGE}
+    assert _words(detail[detail[:, 0] == pr.GROW][:, 1]) == {0, 1, 2, 3} == _words(detail[detail[:, 0] != pr.GROW][:, 1])
+    # grown children in different words, and singly internal nodes of the grown trees in word 3 (the recount's last ballot)
+    grown = [(nt[d[1]]["left"] // 64, nt[d[1]]["right"] // 64) for nt, d in zip(new, detail) if d[0] == pr.GROW and d[3] == 0]
+    assert any(a != b for a, b in grown)
+    assert all(any(s >= 192 for s in pr.singly_internal(nt)) for nt, d in zip(new, detail) if d[0] == pr.GROW and d[3] == 0)
+
+
+@pytest.mark.parametrize("L", [63, 64, 65, 128, 129, 192, 193, 255])
+def test_spread_L_reaches_every_word_of_the_container(L):
+    c, trees, new, detail, _ = _edge("spread_%d" % L)
+    assert _words(detail[:, 1]) == set(range((L + 63) // 64))
+    assert (trees["active"][:, L - 1] == 1).any()
+
+
+def test_idle_pairs_are_taken_by_grows():
+    for name, sets in (("idle_pairs_255", pr.IDLE_PAIRS[255]), ("idle_pairs_256", pr.IDLE_PAIRS[256]), ("idle_pairs_odd", pr.IDLE_PAIRS_ODD)):
+        c, trees, new, detail, _ = _edge(name)
+        taken = {}
+        for k, (nt, d) in enumerate(zip(new, detail)):
+            if d[0] == pr.GROW and d[3] == 0:
+                assert (int(nt[d[1]]["left"]), int(nt[d[1]]["right"])) == tuple(sets[k % c.m][:2])
+                taken[k % c.m] = taken.get(k % c.m, 0) + 1
+        assert sorted(taken) == list(range(c.m)), (name, taken)
+    pairs = [s[:2] for s in pr.IDLE_PAIRS[255] + pr.IDLE_PAIRS[256]] + pr.IDLE_PAIRS_ODD
+    assert {(63, 64), (127, 128), (191, 192), (254, 255), (5, 255), (64, 65)} <= set(pairs)
+
+
+def test_idle_short_grows_are_refused():
+    for name in ("idle_short_one", "idle_short_none"):
+        c, trees, new, detail, _ = _edge(name)
+        grows = detail[detail[:, 0] == pr.GROW]
+        assert len(grows) and set(grows[:, 3].tolist()) <= {2, 3} and (grows[:, 3] == 3).any()
+        assert (detail[detail[:, 0] != pr.GROW][:, 3] != 3).all()
+
+
+@pytest.mark.parametrize("L", [65, 129, 193, 256])
+def test_last_slot_is_chosen(L):
+    c, trees, new, detail, _ = _edge("last_single_%d" % L)
+    other = detail[detail[:, 0] != pr.GROW]
+    assert len(other) and (other[:, 1] == L - 1).all() and (other[:, 3] == 0).any()
+    c, trees, new, detail, _ = _edge("last_leaf_%d" % L)
+    grows = detail[(detail[:, 0] == pr.GROW) & (detail[:, 3] == 0)]
+    assert (grows[:, 1] == L - 1).any() and (grows[:, 1] == L - 2).any()
+    assert all(nt[L - 1]["left"] == 1 and nt[L - 1]["right"] == 2 for nt, d in zip(new, detail) if d[0] == pr.GROW and d[3] == 0 and d[1] == L - 1)
+
+
+def test_tiny_containers():
+    for L, want in ((1, {pr.GROW: {3}, pr.PRUNE: {1}, pr.CHANGE: {1}}), (2, {pr.GROW: {3}, pr.PRUNE: {1}, pr.CHANGE: {1}})):
+        c, trees, new, detail, _ = _edge("tiny_%d" % L)
+        assert {k: set(detail[detail[:, 0] == k][:, 3].tolist()) for k in want} == want
+    c, trees, new, detail, _ = _edge("tiny_3")
+    ok = [nt for nt, d in zip(new, detail) if d[0] == pr.GROW and d[3] == 0]
+    assert ok and all(nt[0]["left"] == 1 and nt[0]["right"] == 2 and nt["active"].all() for nt in ok)
+    assert {0, 1, 3} <= set(detail[:, 3].tolist())
+
+
+def test_ladders_stop_and_open_where_they_should():
+    causes = set()
+    for name in ("ladders_stop", "ladders_stop_int", "ladders_stop_cat"):
+        c, trees, new, detail, _ = _edge(name)
+        for tree, d in zip(trees, detail):
+            assert int(tree["depth"].max()) >= 12
+            if d[3] == 2:
+                lo, hi = _interval(c, tree, d)
+                causes.add("lo == hi" if c.ft[d[2]] == pr.INT and lo == hi else "nbits < 2" if c.ft[d[2]] == pr.CAT and bin(int(hi)).count("1") < 2 else "?")
+    assert causes == {"lo == hi", "nbits < 2"}
+    seen = set()
+    for name in ("ladders_open", "ladders_open_int", "ladders_open_cat", "ladders_open_cont"):
+        c, trees, new, detail, _ = _edge(name)
+        for tree, d in zip(trees, detail):
+            if d[3] != 0 or d[0] == pr.PRUNE or d[1] == 0:
+                continue
+            lo, hi = _interval(c, tree, d)
+            below = "left" if tree["left"][tree["parent"][d[1]]] == d[1] else "right"
+            kind = int(c.ft[d[2]])
+            full_lo, full_hi = c.bounds[d[2]]
+            if kind == pr.CAT and hi != full_hi:
+                seen.add("cat below " + below)
+            elif kind != pr.CAT and lo > full_lo and hi < full_hi:
+                seen.add(("int", "int", "cont")[kind] + " both")
+    assert seen == {"cat below left", "cat below right", "int both", "cont both"}
+
+
+def test_deep_prior_is_deep():
+    c, trees, new, detail, _ = _edge("deep_prior")
+    depth = np.array([t["depth"][d[1]] for t, d in zip(trees, detail) if d[3] == 0 and d[0] != pr.CHANGE])
+    assert depth.max() >= 59 and ((trees["depth"] * trees["active"]).max(axis=1) == 60).all() and c.L == 256
+
+
+def test_max_leaves_edge():
+    _, trees, _, d127, _ = _edge("max_leaves_127")
+    _, trees128, _, d128, _ = _edge("max_leaves_128")
+    assert trees.tobytes() == trees128.tobytes() == _edge("spread256")[1].tobytes()
+    grows = d127[:, 0] == pr.GROW
+    assert grows.any() and set(d127[grows][:, 3].tolist()) <= {2, 4} and (d127[grows][:, 3] == 4).any()
+    assert ((d128[:, 0] == pr.GROW) & (d128[:, 3] == 0)).any() and not (d128[:, 3] == 4).any()
+
+
+def test_guarded_records_are_met():
+    c, trees, new, detail, _ = _edge("guarded")
+    L = c.L
+    ends = set()
+    for k, (tree, d) in enumerate(zip(trees, detail)):
+        for f in ("left", "right"):
+            assert (tree[f][tree["active"] == 1] <= L).all()
+        assert (tree["parent"][np.flatnonzero(tree["active"])[1:]] <= L).all()
+        outside = [i for i in np.flatnonzero(tree["active"] & (tree["is_leaf"] == 0)) if tree["left"][i] == L or tree["right"][i] == L]
+        assert len(outside) == (1 if k % c.m < 2 else 0) and not set(outside) & set(pr.singly_internal(tree))
+        if d[1] >= 0 and d[0] != pr.PRUNE:
+            ends.add(pr.walk_end(tree, int(d[1])))
+    assert ends == {"root", "outside", "cycle"}
