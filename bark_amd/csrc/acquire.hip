@@ -280,51 +280,6 @@ __global__ __launch_bounds__(ACQ_COND_THREADS) void acq_observe_kernel(const uin
     if (tid == 0 && logpred_out) logpred_out[b] = obs[2];
 }
 
-// Utility of the target kinds (include/bark_hip.h) for one candidate and forest: -(1/S) sum_s g(mu, sd, t_s), s = 0 .. S-1.
-// What does not depend on the target is formed once: the reciprocal of the standard deviation and, for MES, log(sd E).
-// `t` is the same address in every lane (the forest's row of `targets`), so the loads are scalar.
-constexpr double ACQ_SQRT1_2 = 0.70710678118654752440;      // 1 / sqrt(2)
-constexpr double ACQ_INV_SQRT_2PI = 0.39894228040143267794;  // 1 / sqrt(2 pi)
-constexpr double ACQ_SQRT_2PI_E = 4.13273135412249293847;    // sqrt(2 pi e)
-
-template <int KIND>
-__device__ __forceinline__ double acq_target_term(double mu, double var, const double *__restrict__ t, int S) {
-    const double sd = sqrt(var > 0.0 ? var : 0.0);
-    double gs = 0.0;
-    if (KIND == BARK_ACQ_MES) {
-        const double inv = 1.0 / (sd + 1e-7);
-        const double h1 = log(sd * ACQ_SQRT_2PI_E);
-        for (int s = 0; s < S; ++s) {
-            const double gam = (t[s] - mu) * inv;
-            const double cdf = 0.5 * erfc(-gam * ACQ_SQRT1_2);
-            const double pdf = exp(-0.5 * (gam * gam)) * ACQ_INV_SQRT_2PI;
-            double inner = ACQ_SQRT_2PI_E * sd * cdf;
-            if (inner <= 0.0) inner = 1e-10;
-            gs += h1 - (log(inner) - gam * pdf / (2.0 * cdf + 1e-10));
-        }
-    } else if (sd > 0.0) {
-        const double inv = 1.0 / sd;
-        for (int s = 0; s < S; ++s) {
-            const double d = t[s] - mu;
-            const double z = d * inv;
-            const double cdf = 0.5 * erfc(-z * ACQ_SQRT1_2);
-            if (KIND == BARK_ACQ_EI)
-                gs += d * cdf + sd * (exp(-0.5 * (z * z)) * ACQ_INV_SQRT_2PI);
-            else
-                gs += cdf;
-        }
-    } else {  // a point mass at mu; a NaN target stays NaN
-        for (int s = 0; s < S; ++s) {
-            const double d = t[s] - mu;
-            if (KIND == BARK_ACQ_EI)
-                gs += d < 0.0 ? 0.0 : d;
-            else
-                gs += d > 0.0 ? 1.0 : (d <= 0.0 ? 0.0 : d);
-        }
-    }
-    return -(gs / (double)S);
-}
-
 // LDS_TABLE: the forest's image sits in LDS in front of the tile's leaf lists; otherwise only the lists do and M^-1 / w are
 // read from global memory (acq_point.h has the layout and the per-candidate steps).
 // n: candidates of this slab (ccodes (bc, W, cpad) holds their codes), acc: the slab's part of the (3, C) sums, row stride

@@ -206,6 +206,23 @@ int score_forests(const double *fpart, int tiles, int bc, double *rows, hipStrea
 int score_finish(const double *acc, int64_t C, int B, const double *yp, double *values_out, double *mpart, const int32_t *info,
                  double *per_forest_out, double *mixture_out, hipStream_t s);
 
+// fidelity.hip (launchers of bark_fidelity_gain_fitted_hip, leafsystem.hip)
+constexpr int FID_MOMENTS = 6;  // doubles per (forest, candidate) between the moments and the quadrature kernel
+size_t fidelity_moments_lds_bytes(int64_t m);
+// n pairs (query, target) whose codes are qcodes / tcodes (bc, W, cpad) against the bc forests of the chunk: mom
+// (bc, FID_MOMENTS, n) and the values of the pairs that need no quadrature in g (bc, n).  targets (bc, S) and weights (bc) or
+// null are the chunk's rows; a forest of weight 0 is skipped (its row of g is NaN)
+int fidelity_moments(const uint32_t *qcodes, const uint32_t *tcodes, int W, int cpad, int n, const double *wvec, const double *Minv,
+                     int R, const double *noise, const double *scale, int m, int bc, const double *targets, int S,
+                     const double *weights, double *mom, double *g, hipStream_t s);
+// the separated pairs of mom -> g; grid (lo, hi, n_a, pad, G) as in include/bark_hip.h
+int fidelity_quadrature(const double *mom, int n, int bc, const double *targets, int S, double lo, double hi, int n_a, double pad,
+                        int G, double *g, hipStream_t s);
+// acc (n) takes the chunk's rows of g in forest order (first: it starts at zero); then, after the last chunk, the gains
+int fidelity_accumulate(const double *g, int n, int bc, const double *weights, int first, double *acc, hipStream_t s);
+int fidelity_finish(const double *acc, int C, int B, const double *weights, const int32_t *info, double *gain_out,
+                    double *per_forest_out, hipStream_t s);
+
 constexpr size_t STAGE_BYTES = 64 * 1024;  // bark_ctx::stage_host / stage_dev
 constexpr int NODE_BYTES = 26;          // forest.py:8-19, packed
 constexpr uint32_t LEAF_FLAG = 0x80000000u;

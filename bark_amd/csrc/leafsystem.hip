@@ -721,6 +721,91 @@ int bark_acquisition_scan_fitted_weighted_hip(bark_ctx *ctx, const void *packed,
                        workspace, workspace_bytes, Bc, stream_);
 }
 
+// ---- information gain of a (query, target) pair from the state (include/bark_hip.h; kernels in fidelity.hip) ----
+
+constexpr int64_t FID_MAX_CAND = 1 << 16, FID_MAX_ADAPT = 1024, FID_MAX_GRID = 4096;
+
+// The workspace of the gain: the codes of the C query and the C target points for Bc forests, the moments of the chunk's
+// pairs, their values (unused when the caller takes per_forest_out: the kernels then write the chunk's rows there), and the
+// running sums.
+struct FidelityAreas {
+    int64_t W, cpad;
+    uint32_t *qcodes, *tcodes;
+    double *mom, *g, *acc;
+    size_t total;
+};
+static FidelityAreas fidelity_areas(void *workspace, int64_t R, int64_t Bc, int64_t C) {
+    FidelityAreas a;
+    a.W = (R + 31) / 32;
+    a.cpad = round_up(C, TILE);
+    const size_t nb = (size_t)Bc;
+    Carve cv{static_cast<char *>(workspace)};
+    a.qcodes = cv.take<uint32_t>(nb * a.W * a.cpad);
+    a.tcodes = cv.take<uint32_t>(nb * a.W * a.cpad);
+    a.mom = cv.take<double>(nb * FID_MOMENTS * C);
+    a.g = cv.take<double>(nb * C);
+    a.acc = cv.take<double>((size_t)C);
+    a.total = cv.o;
+    return a;
+}
+static bool fidelity_shape_ok(int64_t max_bits, int64_t m, int64_t C, int64_t S) {
+    return posterior_shape_ok(max_bits, m, 1) && C >= 1 && C <= FID_MAX_CAND && S >= 1 && S <= ACQ_MAX_TARGETS;
+}
+
+// the targets stay where the caller has them and Z_s lives in LDS: S is checked, and adds nothing
+size_t bark_fidelity_gain_fitted_workspace_bytes(int64_t max_bits, int64_t m, int64_t Bc, int64_t C, int64_t S) {
+    if (Bc < 1 || !fidelity_shape_ok(max_bits, m, C, S)) return 0;
+    return fidelity_areas(nullptr, max_bits, Bc > 65535 ? 65535 : Bc, C).total;
+}
+
+// Per chunk: the two walks, the moments of every pair (which settle the pairs a forest does not separate), the quadrature of
+// the others, and the chunk's values added to the sums in forest order; the finish after the last chunk.  The state is only
+// read.  Every argument is checked before the context is, so a refusal needs no device.
+int bark_fidelity_gain_fitted_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, int64_t d, const double *noise,
+                                  const double *scale, const void *state, size_t state_bytes, const double *query,
+                                  const double *target, int64_t C, const double *targets, int64_t S, const double *weights,
+                                  double lo, double hi, int64_t n_a, double pad, int64_t G, double *gain_out, double *per_forest_out,
+                                  int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc, void *stream_) {
+    static const char *name = "bark_fidelity_gain_fitted_hip";
+    error_buffer()[0] = 0;
+    if (!info || !query || !target || !targets || !gain_out) return fail(BARK_ERR_ARG, "%s: null argument", name);
+    if (!posterior_shape_ok(info->max_bits, info->m, 1))
+        return fail(BARK_ERR_ARG, "%s: at most %d trees and 8192 leaves per forest (got m = %lld, R = %lld)", name, ACQ_MAX_TREES,
+                    (long long)info->m, (long long)info->max_bits);
+    if (C < 1 || C > FID_MAX_CAND) return fail(BARK_ERR_ARG, "%s: between 1 and %lld pairs (got %lld)", name, (long long)FID_MAX_CAND, (long long)C);
+    if (S < 1 || S > ACQ_MAX_TARGETS)
+        return fail(BARK_ERR_ARG, "%s: between 1 and %lld targets per forest (got %lld)", name, (long long)ACQ_MAX_TARGETS, (long long)S);
+    if (n_a < 2 || n_a > FID_MAX_ADAPT)
+        return fail(BARK_ERR_ARG, "%s: between 2 and %lld support points (got %lld)", name, (long long)FID_MAX_ADAPT, (long long)n_a);
+    if (G < 2 || G > FID_MAX_GRID)
+        return fail(BARK_ERR_ARG, "%s: between 2 and %lld quadrature points (got %lld)", name, (long long)FID_MAX_GRID, (long long)G);
+    if (!std::isfinite(lo) || !std::isfinite(hi) || !std::isfinite(pad) || !(lo < hi) || !(pad >= 0.0))
+        return fail(BARK_ERR_ARG, "%s: the grid needs finite lo < hi and a finite pad >= 0 (got %g, %g, %g)", name, lo, hi, pad);
+    FittedCall fc;
+    int rc;
+    if ((rc = fc.open(name, ctx, packed, info, d, noise, scale, state, state_bytes, info_out, workspace, Bc, stream_))) return rc;
+    const FidelityAreas a = fidelity_areas(workspace, fc.R, fc.Bc, C);
+    if (workspace_bytes < a.total) return fail(BARK_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, a.total);
+    const int R = fc.R, m = fc.m, W = (int)a.W, n = (int)C, cpad = (int)bark_leaf_npad(C);
+    const PosteriorState &st = fc.st;
+    if ((rc = fc.copy_info(st.info, info_out, (int)fc.B))) return rc;
+    for (int64_t c0 = 0; c0 < fc.B; c0 += fc.Bc) {
+        const int bc = (int)(fc.B - c0 < fc.Bc ? fc.B - c0 : fc.Bc);
+        bark_pack_info sub;
+        const char *packed_c = fc.chunk(c0, bc, sub);
+        const double *tg = targets + (size_t)c0 * S, *wt = weights ? weights + c0 : nullptr;
+        double *g = per_forest_out ? per_forest_out + (size_t)c0 * C : a.g;  // (bc, C) either way
+        if ((rc = walk_one_hot(packed_c, &sub, query, C, fc.d, W, a.qcodes, ctx->fault, fc.caller))) return rc;
+        if ((rc = walk_one_hot(packed_c, &sub, target, C, fc.d, W, a.tcodes, ctx->fault, fc.caller))) return rc;
+        rc = fidelity_moments(a.qcodes, a.tcodes, W, cpad, n, st.w + (size_t)c0 * R, st.Minv + (size_t)c0 * R * R, R, noise + c0,
+                              scale + c0, m, bc, tg, (int)S, wt, a.mom, g, fc.caller);
+        if (rc || (rc = fidelity_quadrature(a.mom, n, bc, tg, (int)S, lo, hi, (int)n_a, pad, (int)G, g, fc.caller))) return rc;
+        if ((rc = fidelity_accumulate(g, n, bc, wt, c0 == 0, a.acc, fc.caller))) return rc;
+        if ((rc = fc.fault_info(info_out + c0, bc))) return rc;
+    }
+    return fidelity_finish(a.acc, n, (int)fc.B, weights, info_out, gain_out, per_forest_out, fc.caller);
+}
+
 // The state conditioned in place on P more points, in the order given (acq_condition_kernel on the state's M^-1; w does not
 // change).  A fault of the walk marks the state's status too: its M^-1 has then been conditioned on a leaf that means nothing.
 int bark_leaf_posterior_condition_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, int64_t d, const double *noise,

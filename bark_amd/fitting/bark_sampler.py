@@ -4,7 +4,9 @@ Per step: ONE launch draws the proposals of every tree of every chain (`tree_pro
 `LeafChainBatch` or `ChainBatch` decides them on the device, a second launch copies the accepted trees over the forests, which
 stay resident in HBM between steps, and the noise / scale half follows (`noise_scale_proposals`, `step_noise_scale`).  The
 proposals come back to the host once per step because the sweeps' packer and step tables are host code; a step loop that never
-returns to the host, the multi-fidelity sampler and the BoFire glue (domain objects) are not part of this module.
+returns to the host and the BoFire glue (domain objects) are not part of this module.  Multi-fidelity problems need no sampler
+of their own: the fidelity is an input column the trees split on like any other, and which fidelity to evaluate is chosen from
+the fitted posterior (`bark_amd.optimizer.propose_fidelity_information_based`).
 
 Random numbers are Philox4x32-10 addressed by (seed, step, chain, tree): a run is a function of its seed, and is not the
 reference's numba stream."""

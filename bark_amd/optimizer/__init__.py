@@ -7,5 +7,7 @@ from .acquisition import (acquisition_plan, acquisition_scan, propose_batch_from
 from .constraints import LinearConstraints  # noqa: F401
 from .domain import (CellBoxes, CellTable, cell_boxes, domain_candidates, domain_neighbours, domain_plan,  # noqa: F401
                      domain_repair, propose_from_domain, split_table)
+from .fidelity import (fidelity_information_gain, fstar_at_fidelity, information_gain,  # noqa: F401
+                       propose_fidelity_information_based, with_fidelity)
 from .thompson_sampling import (propose_thompson_from_candidates, propose_thompson_from_domain,  # noqa: F401
                                 thompson_forests)

@@ -178,6 +178,14 @@ class LeafPosterior:
         out = (float(best.item()), int(idx.item()))
         return (*out, acq.cpu().numpy()) if return_values else out
 
+    def information_gain(self, query, target, targets, **kwargs):
+        """-> gains (C,): what a value at query[c] tells about the minimum of the function target[c] lies on, whose draws are
+        targets (B, S) — `bark_amd.optimizer.fidelity.information_gain(self, ...)`, which documents grid=, per_forest=, chunk=
+        and weights=.  The state is not modified."""
+        from ..optimizer.fidelity import information_gain
+
+        return information_gain(self, query, target, targets, **kwargs)
+
     def condition_(self, points, values=None) -> "LeafPosterior":
         """Condition the state in place on `points` (P <= 64, d), in the order given, as `acquisition_scan(pending=points)`
         conditions its own M^-1: one rank-one downdate per point and forest, w unchanged.  A later `scan()` equals the

@@ -591,6 +591,62 @@ int bark_leaf_posterior_gather_hip(const void *state_in, int64_t B_in, int64_t R
                                    void *state_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Information gain of a (query, target) pair from a fitted posterior: which fidelity is worth paying for.  The reference
+ * (information_based_fidelity.py:16-36, 90-167) makes the fidelity an input feature; given a proposed x it asks, per fidelity l,
+ * how much observing f(x, l) tells about the minimum f* of the target-fidelity function, and divides by the cost.
+ * BARK_ACQ_MES above is the l = target half; this entry point is the whole of it.  It reads the state of
+ * bark_leaf_posterior_fit_hip and does not know which column is the fidelity:
+ *   query  (C, d) device: query[c] is the point that would be evaluated;
+ *   target (C, d) device: target[c] is the point whose function's minimum the draws targets[b][s] ((B, S) device) describe.
+ * Per forest b and pair c, with a_0 < a_1 < ... the leaves of query[c] and b_0 < b_1 < ... those of target[c] (code-bit order):
+ *   mu_m, var_m of query[c] and mu_0, var_0 of target[c] exactly as the scan forms mu_b(x), var_b(x) (same sums, same order);
+ *   cov = (scale_b / m) sum_i sum_j (M_b^-1)[a_i][b_j], i in the outer loop, j in the inner loop, one accumulator from 0.0:
+ *   the posterior covariance of the two values, one more bilinear form in the M^-1 of the state;
+ *   sd = sqrt(max(var, 0)); E, Phi, phi as for BARK_ACQ_MES.  Grid parameters (lo, hi, n_a, pad, G); the reference's are
+ *   (-10, 10, 100, 0.25, 250).  The rules, in this order:
+ *   1. sd_m == 0: g = -inf, as for BARK_ACQ_MES.
+ *   2. the two leaf lists are equal (query[c] == target[c] among others): g = (1/S) sum_s of the BARK_ACQ_MES g on
+ *      (mu_m, sd_m, t_s), s = 0 .. S-1 — the same device function as the scan's, so the bits are the scan's.
+ *      DEVIATION: the reference decides this by `fidelity == 0`, per call; here every forest decides for itself.  A forest
+ *      whose trees do not separate the two points sees ONE random variable, whose entropy given f* is the closed form; the
+ *      reference's quadrature with s^2 = 0 only approximates it.
+ *   3. otherwise (the reference's _entropy_low_fidelity with its guards):
+ *        H1 = log(sd_m E),  s2 = var_0 - cov^2 / (var_m + 1e-9),  u(f) = mu_0 + cov (f - mu_m) / (var_m + 1e-9)
+ *        Psi_s(f) = Phi((t_s - u(f)) / (sqrt(max(s2, 0)) + 1e-9)) phi((f - mu_m) / (sd_m + 1e-9))
+ *        Z_s = 1 / (Phi((t_s - mu_0) / (sd_0 + 1e-9)) sd_m + 1e-10)
+ *      support: f_k = lo + k (hi - lo) / (n_a - 1), k live when sum_s |Psi_s(f_k)| > 1e-8; fmin = min live f_k - pad,
+ *        fmax = max live f_k + pad; no live k: g = NaN (the reference would raise).
+ *      quadrature: f_j = fmin + j (fmax - fmin) / (G - 1), y_{s,j} = xlogy(z, z) with z = Z_s Psi_s(f_j) (0 at z == 0),
+ *        I_s the uniform trapezoid of y_{s,.}, H2 = -(1/S) sum_s I_s, g = H1 - H2.
+ *      max(s2, 0) is a guard the reference lacks (it takes the root of a negative s2 and asserts on the NaN).
+ *      The quotients by sd_m + 1e-9, sd_0 + 1e-9 and sqrt(max(s2, 0)) + 1e-9 are products with one reciprocal per pair.
+ *   gain_out[c] = sum_b wgt_b g_{b,c}: with weights == NULL the plain sum over b divided once by B (as the scan's finish does);
+ *   with weights (device, (B,), normalised by the caller) every g is multiplied by weights[b] before it is added, nothing is
+ *   divided, and a forest of weight exactly 0.0 is skipped whole, as in the weighted scan.  The gain is not negated: the
+ *   caller maximises it.  per_forest_out (B, C) or NULL: g_{b,c} itself; NaN rows for skipped and for failed forests.
+ * Order (part of the contract).  Forests strictly b = 0 .. B-1 across chunks.  Inside a separated pair: the sum over s of
+ *   |Psi_s(f_k)| runs s = 0 .. S-1; at every quadrature point j the column q_j = sum_s y_{s,j} runs s = 0 .. S-1; one wave of
+ *   64 lanes owns the pair, lane l adds w_j q_j (w = 1/2 at j = 0 and G - 1, else 1) for j = l, l + 64, ... in that order from
+ *   0.0, the 64 lane sums meet in a xor butterfly (offsets 32, 16, 8, 4, 2, 1), the result is multiplied by (fmax - fmin) /
+ *   (G - 1) and divided by S.  The result therefore does not depend on Bc, bit for bit, and two runs give the same bits.
+ * info_out[b]: the state's status, or -1 for an invalid categorical value in query or target; a non-zero entry of a forest
+ *   of non-zero weight makes every gain NaN.
+ * Limits, refused with BARK_ERR_ARG before any launch (and before the context is looked at): m <= 64, R <= 8192,
+ *   1 <= C <= 65536, 1 <= S <= 1024, 2 <= n_a <= 1024, 2 <= G <= 4096, lo < hi and pad >= 0, all finite; a null query, target,
+ *   targets or gain_out; then the fitted calls' (state size and alignment).  The call only enqueues: no allocation, no host
+ *   synchronisation.  M^-1 is read from global memory.
+ * workspace >= bark_fidelity_gain_fitted_workspace_bytes(R, m, Bc, C, S) (pure host code; 0 for a refused shape): the codes
+ *   of the 2 C points for Bc forests, 7 Bc C + C doubles.  S is checked but adds nothing: the targets stay where they are.
+ * ------------------------------------------------------------------------------------- */
+size_t bark_fidelity_gain_fitted_workspace_bytes(int64_t max_bits, int64_t m, int64_t Bc, int64_t C, int64_t S);
+int bark_fidelity_gain_fitted_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, int64_t d, const double *noise,
+                                  const double *scale, const void *state, size_t state_bytes, const double *query /* (C, d) */,
+                                  const double *target /* (C, d) */, int64_t C, const double *targets /* (B, S) */, int64_t S,
+                                  const double *weights /* (B,) or NULL */, double lo, double hi, int64_t n_a, double pad,
+                                  int64_t G, double *gain_out /* (C,) */, double *per_forest_out /* (B, C) or NULL */,
+                                  int32_t *info_out /* (B,) */, void *workspace, size_t workspace_bytes, int64_t Bc, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Sample paths from a fitted posterior (Thompson sampling).  A tree kernel has finite rank, so a posterior draw of forest b
  * is exactly a table of R leaf weights, W ~ N(c_b w_b, (scale_b / m) M_b^-1), and the sample path is the function
  * f(x) = sum_t W[col_t(x)]: once the table exists it is evaluated anywhere, later, with m gathers per point.
