@@ -61,6 +61,28 @@ __device__ __forceinline__ void point_sums(const unsigned short *idx, int cnt, c
     }
 }
 
+// sum over the workgroup's 256 threads of two values each, the same tree whatever the values: xor butterfly within a wave
+// (every lane ends with the wave's sum), then waves 0 .. 3 in order by thread 0, which alone holds the result.
+// red: 8 doubles in LDS that no thread touches between the caller's barrier before this call and its next one after it.
+// The score kernels (scores.hip) and the predict kernels (predict.hip) sum their tiles with this one tree.
+__device__ __forceinline__ void tile_sum2(double &u, double &v, double *red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        u += __shfl_xor(u, o);
+        v += __shfl_xor(v, o);
+    }
+    const int wave = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        red[wave] = u;
+        red[4 + wave] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u = ((red[0] + red[1]) + red[2]) + red[3];
+        v = ((red[4] + red[5]) + red[6]) + red[7];
+    }
+}
+
 // Utility of the target kinds (include/bark_hip.h) for one candidate and forest: -(1/S) sum_s g(mu, sd, t_s), s = 0 .. S-1.
 // What does not depend on the target is formed once: the reciprocal of the standard deviation and, for MES, log(sd E).
 // `t` is the same address in every lane (the forest's row of `targets`), so the loads are scalar.

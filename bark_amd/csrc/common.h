@@ -206,6 +206,30 @@ int score_forests(const double *fpart, int tiles, int bc, double *rows, hipStrea
 int score_finish(const double *acc, int64_t C, int B, const double *yp, double *values_out, double *mpart, const int32_t *info,
                  double *per_forest_out, double *mixture_out, hipStream_t s);
 
+// predict.hip (launchers of bark_leaf_posterior_predict_hip, leafsystem.hip)
+// n points of one slab against the bc forests of the chunk, as score_scan: West's recurrence per point in the slab's part of
+// acc (4, C; row stride astride).  weights: the chunk's rows of the normalised weights, or null (every forest weighs wq);
+// info: the chunk's status in the state; fmu / fvar: the chunk's first rows of the per-forest output (row stride fstride) or
+// null.  scores: also yp, sacc (3, C; score_scan's rows) and fpart (bc, tiles, 2) from tile0 on
+int predict_scan(int variant, bool scores, const uint32_t *ccodes, int W, int cpad, int n, const double *wvec, const double *Minv,
+                 const double *tab, int R, const double *noise, const double *scale, int m, int bc, const int32_t *info,
+                 const double *weights, double wq, int observation, const double *yp, int first, double *acc, size_t astride,
+                 double *sacc, double *fmu, double *fvar, size_t fstride, double *fpart, int tiles, int tile0, hipStream_t s);
+// out[q ostride + c], q < Q <= 16, c < n: the mixture's quantiles from the stored rows of all B forests; probs / zscores: host
+int predict_quantiles(const double *fmu, const double *fvar, size_t fstride, int n, int B, const double *weights, double wq,
+                      const double *probs, const double *zscores, int Q, const int32_t *flag, double *out, size_t ostride,
+                      hipStream_t s);
+// *flag = a forest of non-zero weight has a non-zero status
+int predict_flag(const int32_t *info, const double *weights, int B, int32_t *flag, hipStream_t s);
+// moments_out (2, C) from acc; under the flag NaN there and in quantiles_out (Q, C); NaN rows of forest_out (2, B, C) or null
+// for the forests with a non-zero status
+int predict_finish(const double *acc, int64_t C, int B, const int32_t *info, const int32_t *flag, double *moments_out,
+                   double *forest_out, double *quantiles_out, int Q, hipStream_t s);
+// score_finish for the weighted mixture (weights null: that function's arithmetic); mpart (tiles, 2)
+int predict_score_finish(const double *acc, const double *sacc, int64_t C, int B, const double *weights, const double *yp,
+                         double *values_out, double *mpart, const int32_t *info, const int32_t *flag, double *per_forest_out,
+                         double *mixture_out, hipStream_t s);
+
 // fidelity.hip (launchers of bark_fidelity_gain_fitted_hip, leafsystem.hip)
 constexpr int FID_MOMENTS = 6;  // doubles per (forest, candidate) between the moments and the quadrature kernel
 size_t fidelity_moments_lds_bytes(int64_t m);

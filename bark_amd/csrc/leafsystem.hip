@@ -4,7 +4,7 @@
 // entry point checks its own arguments, says what it keeps in the workspace (LeafNeeds), opens the system and hands
 // for_chunks a body that lists the steps it takes.
 // The kernels are elsewhere: the R x R Cholesky sweep in chol.hip (reached through SystemSweep, common.h), the leaf-space
-// kernels in leafspace.hip, sample.hip, acquire.hip and scores.hip; this unit's only kernels move status words
+// kernels in leafspace.hip, sample.hip, acquire.hip, scores.hip and predict.hip; this unit's only kernels move status words
 // (fault_info_kernel, copy_info_kernel).
 // A fitted posterior (bark_leaf_posterior_*_hip, bark_acquisition_scan_fitted_hip) is the part of that state which outlives
 // a call: M^-1, w and the sweep's status of all B forests in a buffer of the caller's (PosteriorState).
@@ -876,6 +876,135 @@ int bark_leaf_posterior_observe_hip(bark_ctx *ctx, const void *packed, const bar
         if (rc || (rc = fc.fault_info(st.info + c0, bc))) return rc;
     }
     return fc.copy_info(st.info, info_out, (int)fc.B);
+}
+
+// ---- predictions from the state (include/bark_hip.h; kernels in predict.hip) ----
+
+constexpr int64_t PRED_MAX_PROBS = 16;
+
+// The workspace of the predict call: the codes of one slab of points for Bc forests, the LDS image when that variant runs,
+// the (4, C) recurrence state, the flag word, with scores the (3, C) score state and the tile partials of the mixture
+// (tiles, 2) and of all B forests (B, tiles, 2: the slabs are the outer loop, so a forest's tiles are complete only at the
+// end), and mu_b / var_b of one slab (2, B, slab) when quantiles are asked for and forest_out does not hold them.
+struct PredictAreas {
+    int64_t W, cpad, slab;
+    uint32_t *ccodes;
+    double *tab, *acc, *sacc, *mpart, *fpart, *fslab;
+    int32_t *flag;
+    size_t total;
+};
+static PredictAreas predict_areas(void *workspace, int64_t R, int64_t B, int64_t Bc, int64_t C, int64_t Q, bool want_forest,
+                                  bool want_scores, bool lds_table) {
+    PredictAreas a;
+    a.W = (R + 31) / 32;
+    a.slab = C < ACQ_SLAB ? C : ACQ_SLAB;
+    a.cpad = round_up(a.slab, TILE);
+    const size_t nb = (size_t)Bc, tiles = (size_t)acq_partials(C);
+    Carve cv{static_cast<char *>(workspace)};
+    a.ccodes = cv.take<uint32_t>(nb * a.W * a.cpad);
+    a.tab = cv.take<double>(lds_table ? nb * acq_table_doubles(R) : 0);
+    a.acc = cv.take<double>((size_t)4 * C);
+    a.flag = cv.take<int32_t>(1);
+    a.sacc = cv.take<double>(want_scores ? (size_t)3 * C : 0);
+    a.mpart = cv.take<double>(want_scores ? 2 * tiles : 0);
+    a.fpart = cv.take<double>(want_scores ? (size_t)B * 2 * tiles : 0);
+    a.fslab = cv.take<double>(Q > 0 && !want_forest ? (size_t)2 * B * a.slab : 0);
+    a.total = cv.o;
+    return a;
+}
+
+size_t bark_leaf_posterior_predict_workspace_bytes(int64_t max_bits, int64_t m, int64_t B, int64_t Bc, int64_t C, int64_t Q,
+                                                   int want_forest, int want_scores, int variant) {
+    int var = 0;
+    if (B < 1 || Bc < 1 || C < 1 || C > (1 << 24) || Q < 0 || Q > PRED_MAX_PROBS || bark_acquisition_plan(max_bits, m, variant, &var, nullptr)) {
+        error_buffer()[0] = 0;  // a query reports through its value only
+        return 0;
+    }
+    if (Bc > B) Bc = B;
+    if (Bc > 65535) Bc = 65535;
+    return predict_areas(nullptr, max_bits, B, Bc, C, Q, want_forest != 0, want_scores != 0, var == 1).total;
+}
+
+// Slab by slab of points, and inside a slab chunk by chunk of forests: the walk and predict_scan_kernel; after a slab's last
+// chunk its quantiles, from the rows the scan stored.  The finish after the last slab.  The state is only read.  Every
+// argument is checked before the context is, so a refusal needs no device.
+int bark_leaf_posterior_predict_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, int64_t d, const double *noise,
+                                    const double *scale, const void *state, size_t state_bytes, const double *points, int64_t C,
+                                    const double *weights, int observation, const double *y_points, const double *probs,
+                                    const double *zscores, int64_t Q, int variant, double *moments_out, double *forest_out,
+                                    double *quantiles_out, double *per_forest_out, double *mixture_out, double *values_out,
+                                    int32_t *info_out, void *workspace, size_t workspace_bytes, int64_t Bc, void *stream_) {
+    static const char *name = "bark_leaf_posterior_predict_hip";
+    error_buffer()[0] = 0;
+    if (!info || !points || !moments_out || !state) return fail(BARK_ERR_ARG, "%s: null argument", name);
+    if (C < 1 || C > (1 << 24)) return fail(BARK_ERR_ARG, "%s: bad shape C=%lld", name, (long long)C);
+    if (Q < 0 || Q > PRED_MAX_PROBS)
+        return fail(BARK_ERR_ARG, "%s: between 0 and %lld probabilities per call (got %lld)", name, (long long)PRED_MAX_PROBS, (long long)Q);
+    if (Q > 0 && (!probs || !zscores)) return fail(BARK_ERR_ARG, "%s: quantiles need probs and zscores", name);
+    if ((Q > 0) != (quantiles_out != nullptr)) return fail(BARK_ERR_ARG, "%s: quantiles_out is given exactly when Q > 0", name);
+    for (int64_t q = 0; q < Q; ++q)
+        if (!(probs[q] > 0.0 && probs[q] < 1.0) || !std::isfinite(zscores[q]))
+            return fail(BARK_ERR_ARG, "%s: every probability must lie strictly inside (0, 1), with a finite zscore (got %g, %g)", name,
+                        probs[q], zscores[q]);
+    const bool want_scores = y_points != nullptr;
+    if (want_scores != (per_forest_out != nullptr) || want_scores != (mixture_out != nullptr))
+        return fail(BARK_ERR_ARG, "%s: y_points, per_forest_out and mixture_out are given together or not at all", name);
+    if (values_out && !want_scores) return fail(BARK_ERR_ARG, "%s: values_out needs y_points", name);
+    if (observation != 0 && observation != 1) return fail(BARK_ERR_ARG, "%s: observation is 0 or 1 (got %d)", name, observation);
+    int var = 0, rc;
+    if ((rc = bark_acquisition_plan(info->max_bits, info->m, variant, &var, nullptr))) return rc;
+    if (info->B < 1) return fail(BARK_ERR_ARG, "%s: bad shape B=%lld", name, (long long)info->B);
+    const size_t need_state = posterior_state(nullptr, info->max_bits, info->B).total;
+    if (state_bytes < need_state) return fail(BARK_ERR_ARG, "%s: state buffer too small: %zu < %zu bytes", name, state_bytes, need_state);
+    if (reinterpret_cast<uintptr_t>(state) & 255) return fail(BARK_ERR_ARG, "%s: state and workspace must be 256-byte aligned", name);
+    FittedCall fc;
+    if ((rc = fc.open(name, ctx, packed, info, d, noise, scale, state, state_bytes, info_out, workspace, Bc, stream_))) return rc;
+    const int R = fc.R, m = fc.m, B = (int)fc.B;
+    const PredictAreas a = predict_areas(workspace, R, B, fc.Bc, C, Q, forest_out != nullptr, want_scores, var == 1);
+    if (workspace_bytes < a.total) return fail(BARK_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, a.total);
+    const int W = (int)a.W, tiles = (int)acq_partials(C);
+    const PosteriorState &st = fc.st;
+    const double wq = 1.0 / (double)B;
+    const bool one_chunk = fc.Bc >= fc.B;
+    if ((rc = fc.copy_info(st.info, info_out, B))) return rc;
+    if (var == 1 && one_chunk && (rc = acq_pack(st.Minv, st.w, R, B, a.tab, fc.caller))) return rc;
+    for (int64_t s0 = 0; s0 < C; s0 += ACQ_SLAB) {
+        const int64_t n = C - s0 < ACQ_SLAB ? C - s0 : ACQ_SLAB;
+        // where the scan stores mu_b / var_b of this slab, row b of all B forests at b * fstride: the caller's array or the slab
+        // (an area of no bytes still has an address: the slab is named only when it was asked for)
+        double *slab = Q > 0 && !forest_out ? a.fslab : nullptr;
+        double *fmu = forest_out ? forest_out + s0 : slab;
+        double *fvar = forest_out ? forest_out + (size_t)B * C + s0 : (slab ? slab + (size_t)B * a.slab : nullptr);
+        const size_t fstride = forest_out ? (size_t)C : (size_t)a.slab;
+        for (int64_t c0 = 0; c0 < fc.B; c0 += fc.Bc) {
+            const int bc = (int)(fc.B - c0 < fc.Bc ? fc.B - c0 : fc.Bc);
+            bark_pack_info sub;
+            const char *packed_c = fc.chunk(c0, bc, sub);
+            const double *w = st.w + (size_t)c0 * R, *Minv = st.Minv + (size_t)c0 * R * R;
+            if (var == 1 && !one_chunk && (rc = acq_pack(Minv, w, R, bc, a.tab, fc.caller))) return rc;
+            if ((rc = walk_one_hot(packed_c, &sub, points + (size_t)s0 * fc.d, n, fc.d, W, a.ccodes, ctx->fault, fc.caller))) return rc;
+            rc = predict_scan(var, want_scores, a.ccodes, W, (int)bark_leaf_npad(n), (int)n, w, Minv, a.tab, R, noise + c0, scale + c0, m,
+                              bc, st.info + c0, weights ? weights + c0 : nullptr, wq, observation,
+                              want_scores ? y_points + s0 : nullptr, c0 == 0, a.acc + s0, (size_t)C, want_scores ? a.sacc + s0 : nullptr,
+                              fmu ? fmu + (size_t)c0 * fstride : nullptr, fmu ? fvar + (size_t)c0 * fstride : nullptr, fstride,
+                              want_scores ? a.fpart + (size_t)c0 * tiles * 2 : nullptr, tiles, (int)(s0 / ACQ_TILE), fc.caller);
+            if (rc || (rc = fc.fault_info(info_out + c0, bc))) return rc;
+        }
+        if (Q > 0) {
+            if ((rc = predict_flag(info_out, weights, B, a.flag, fc.caller))) return rc;
+            rc = predict_quantiles(fmu, fvar, fstride, (int)n, B, weights, wq, probs, zscores, (int)Q, a.flag, quantiles_out + s0, (size_t)C,
+                                   fc.caller);
+            if (rc) return rc;
+        }
+    }
+    if ((rc = predict_flag(info_out, weights, B, a.flag, fc.caller))) return rc;
+    if (want_scores) {
+        if ((rc = score_forests(a.fpart, tiles, B, per_forest_out, fc.caller))) return rc;
+        rc = predict_score_finish(a.acc, a.sacc, C, B, weights, y_points, values_out, a.mpart, info_out, a.flag, per_forest_out,
+                                  mixture_out, fc.caller);
+        if (rc) return rc;
+    }
+    return predict_finish(a.acc, C, B, info_out, a.flag, moments_out, forest_out, quantiles_out, (int)Q, fc.caller);
 }
 
 // Predictive scores (include/bark_hip.h, kernels in scores.hip): the scan's sequence with the points in place of the

@@ -25,27 +25,6 @@ namespace {
 
 constexpr double SCORE_TWO_PI = 6.28318530717958647693;
 
-// sum over the workgroup's 256 threads of two values each, the same tree whatever the values: xor butterfly within a wave
-// (every lane ends with the wave's sum), then waves 0 .. 3 in order by thread 0, which alone holds the result.
-// red: 8 doubles in LDS that no thread touches between the caller's barrier before this call and its next one after it.
-__device__ __forceinline__ void tile_sum2(double &u, double &v, double *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        u += __shfl_xor(u, o);
-        v += __shfl_xor(v, o);
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[wave] = u;
-        red[4 + wave] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u = ((red[0] + red[1]) + red[2]) + red[3];
-        v = ((red[4] + red[5]) + red[6]) + red[7];
-    }
-}
-
 // Arguments as acq_scan_kernel's (LDS_TABLE, ccodes, n, acc / astride, first), and: info (bc) the sweep's status of the chunk's
 // forests (a failed forest counts as mu = var = NaN), yp the targets of the slab's points, fpart (bc, tiles, 2) with this
 // workgroup's tile at tile0 + blockIdx.x.  Rows of acc: running maximum of l over the forests so far, sum of exp(l - maximum),

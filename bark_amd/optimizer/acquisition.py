@@ -298,21 +298,39 @@ def propose_batch_from_candidates(model, data, candidates, domain, q: int, kappa
 
 
 def propose_mes_from_candidates(model, data, candidates, domain, num_samples: int = 100, generator=None,
-                                chunk: int | None = None, variant: str = "auto", pending=None, skip=None, posterior=None):
+                                chunk: int | None = None, variant: str = "auto", pending=None, skip=None, posterior=None,
+                                seed: int = 0, return_info: bool = False):
     """The candidate row with the largest information gain about the minimum value: the workflow of the reference's
     `propose_fidelity_information_based` (information_based_fidelity.py:16-36) with a candidate set in place of its single x.
     `generate_fstar_samples` draws num_samples joint posterior samples per forest at the training inputs and keeps their
     minima, (B, num_samples) on the device; `acquisition_scan(kind="mes", targets=...)` scores every candidate against
     them and returns the arg-min of the negated gain.  generator: a torch.Generator, an int seed or None, as
-    `generate_fstar_samples` takes it.  posterior: as in `acquisition_scan`, for the scan; the draws of the minimum do not
-    read a fitted state, so `model`, `data` and `domain` are still needed.  Torch candidates give a device row (the index is
-    not read back), numpy candidates a numpy row."""
+    `generate_fstar_samples` takes it.  posterior: as in `acquisition_scan`, for the scan.  Torch candidates give a device
+    row (the index is not read back), numpy candidates a numpy row.
+
+    With a posterior and model or data None, everything comes from the state: the minima are those of
+    `posterior.sample_paths(num_samples, seed=seed)` over the candidates (`LeafPaths.minimise`), (B, num_samples) as
+    `fstar_at_fidelity` arranges them, so after `observe_` the draws follow the observations and no model or data is needed.
+    A forest of weight 0 whose draws are not finite gets zeros: the scan skips it.  `generator` is not used then.
+    return_info: also {"index", "value", "targets"}, the scan's arg-min, its value and the (B, num_samples) minima."""
     import torch
 
     from .thompson_sampling import generate_fstar_samples
 
     if model is None or data is None:
-        raise ValueError("propose_mes_from_candidates draws the minima from model and data: pass them beside the posterior")
+        from ..tree_kernels.posterior import LeafPosterior
+
+        if not isinstance(posterior, LeafPosterior):
+            raise ValueError("propose_mes_from_candidates draws the minima from model and data, or from a LeafPosterior passed as posterior")
+        post = _fitted(posterior, domain)
+        values, _ = post.sample_paths(int(num_samples), seed=seed).minimise(_points(candidates, post.d)[0])
+        fstar = values.reshape(post.B, int(num_samples))
+        if post.log_weights is not None:
+            dead = (post.weights == 0)[:, None] & ~torch.isfinite(fstar)
+            fstar = torch.where(dead, torch.zeros_like(fstar), fstar)
+        value, idx = post.scan(candidates, kind="mes", targets=fstar, chunk=chunk, variant=variant, pending=pending, skip=skip)
+        row = candidates.index_select(0, idx.to(candidates.device).reshape(1))[0] if _is_torch(candidates) else np.asarray(candidates)[idx]
+        return (row, {"index": idx, "value": value, "targets": fstar}) if return_info else row
     train_x, train_y = data
     # torch inputs keep the minima on the device between the two calls
     site_x = train_x if _is_torch(train_x) else torch.as_tensor(np.asarray(train_x, dtype=np.float64), device=_lib.torch_device())

@@ -178,6 +178,123 @@ class LeafPosterior:
         out = (float(best.item()), int(idx.item()))
         return (*out, acq.cpu().numpy()) if return_values else out
 
+    def _predict_weights(self, weights):
+        """`predict`'s and `scores`' weights=: None is the state's own weights (`scan`'s "state"), "equal" forces equal weights,
+        an array is `scan`'s -> None or a float64 device tensor (B,)"""
+        import torch
+
+        w = self._scan_weights(None if isinstance(weights, str) and weights == "equal" else "state" if weights is None else weights)
+        return None if w is None else _lib.to_device(w, torch.float64)
+
+    def _predict(self, points, w_d, observation, y_d, probs, want_forest, want_values, chunk, variant):
+        """One call of bark_leaf_posterior_predict_hip (at most 16 probabilities) -> the device outputs it was asked for"""
+        import statistics
+
+        import torch
+
+        from ..optimizer.acquisition import VARIANTS
+
+        pts_d = points
+        C, B, R, dev = int(pts_d.shape[0]), self.B, self.R, self.state.device
+        Q = len(probs)
+        out = {"moments": torch.empty((2, C), dtype=torch.float64, device=dev)}
+        if want_forest:
+            out["forest"] = torch.empty((2, B, C), dtype=torch.float64, device=dev)
+        if Q:
+            out["quantiles"] = torch.empty((Q, C), dtype=torch.float64, device=dev)
+        if y_d is not None:
+            out["rows"] = torch.empty((B, 2), dtype=torch.float64, device=dev)
+            out["mix"] = torch.empty(2, dtype=torch.float64, device=dev)
+            if want_values:
+                out["values"] = torch.empty((2, C), dtype=torch.float64, device=dev)
+        p_h = np.asarray(probs, dtype=np.float64)
+        z_h = np.asarray([statistics.NormalDist().inv_cdf(float(p)) for p in p_h], dtype=np.float64)
+        lib = _lib.lib()
+        self._call(lib.bark_leaf_posterior_predict_hip,
+                   lambda k: int(lib.bark_leaf_posterior_predict_workspace_bytes(R, self.m, B, k, C, Q, int(want_forest),
+                                                                                 int(y_d is not None), VARIANTS[variant])),
+                   chunk, _lib.ptr(self.state), self.nbytes, _lib.ptr(pts_d), C, _lib.ptr(w_d), int(bool(observation)), _lib.ptr(y_d),
+                   _lib.ptr(p_h if Q else None), _lib.ptr(z_h if Q else None), Q, VARIANTS[variant], _lib.ptr(out["moments"]),
+                   _lib.ptr(out.get("forest")), _lib.ptr(out.get("quantiles")), _lib.ptr(out.get("rows")), _lib.ptr(out.get("mix")),
+                   _lib.ptr(out.get("values")), weights=w_d)
+        return out
+
+    def _predict_args(self, points, variant):
+        from ..optimizer.acquisition import VARIANTS, acquisition_plan
+
+        if variant not in VARIANTS:
+            raise ValueError(f"unknown variant {variant!r} (use 'auto', 'lds' or 'global')")
+        if len(points) < 1:
+            raise ValueError("a prediction needs at least one point")
+        acquisition_plan(self.R, self.m, variant)  # refuses variant="lds" past the LDS limit before anything is allocated
+        return _points(points, self.d)[0]
+
+    def predict(self, points, *, observation: bool = False, per_forest: bool = False, quantiles=None, weights=None,
+                chunk: int | None = None, variant: str = "auto"):
+        """The predictive of the weighted mixture of the forests at `points` (C, d), from the state
+        (bark_leaf_posterior_predict_hip) -> dict:
+
+          "mean", "var" (C,)               the mixture's moments (`mixture_of_gaussians_as_normal` over `forest_predict` for
+                                           equal weights), by a one-pass recurrence in forest order that does not cancel
+          "forest_mean", "forest_var"      (B, C), with `per_forest`: every forest's own posterior; NaN rows for weight 0
+          "quantiles" (Q, C)               with `quantiles=[p, ...]`, each strictly inside (0, 1): the mixture's quantiles (a
+                                           credible band is quantiles=[0.025, 0.975]); more than 16 go in calls of 16
+
+        observation: add every forest's noise s2_b to its variance, the predictive of an observation instead of the latent
+        function.  weights: None uses the state's own importance weights (equal weights while it has none), "equal" forces
+        equal weights, a (B,) array is normalised on the host as in `scan`; a forest of weight exactly 0 is skipped and its
+        status fails nothing.  The state is not modified.  No result depends on `chunk` or `variant`, bit for bit.  Torch
+        points give device tensors, numpy points numpy arrays.  Errors as in `scan`; ValueError when the per-forest output
+        exceeds the memory budget.  No CPU fallback."""
+        probs = [] if quantiles is None else [float(p) for p in np.asarray(quantiles, dtype=np.float64).reshape(-1)]
+        if any(not (0.0 < p < 1.0) for p in probs):
+            raise ValueError(f"quantiles must lie strictly inside (0, 1), got {probs}")
+        pts_d = self._predict_args(points, variant)
+        C = int(pts_d.shape[0])
+        if per_forest:
+            from .tree_gps import _check_output_budget
+
+            _check_output_budget(16 * self.B * C, f"predict(per_forest=True): {self.B} forests at {C} points")
+
+        import torch
+
+        w_d = self._predict_weights(weights)
+        first = self._predict(pts_d, w_d, observation, None, probs[:16], per_forest, False, chunk, variant)
+        out = {"mean": first["moments"][0], "var": first["moments"][1]}
+        if per_forest:
+            out["forest_mean"], out["forest_var"] = first["forest"][0], first["forest"][1]
+        if probs:
+            parts = [first["quantiles"]]
+            for q0 in range(16, len(probs), 16):
+                parts.append(self._predict(pts_d, w_d, observation, None, probs[q0:q0 + 16], False, False, chunk, variant)["quantiles"])
+            out["quantiles"] = parts[0] if len(parts) == 1 else torch.cat(parts)
+        return out if _is_torch(points) else {k: v.cpu().numpy() for k, v in out.items()}
+
+    def scores(self, points, values, *, observation: bool = False, return_values: bool = False, weights=None,
+               chunk: int | None = None, variant: str = "auto"):
+        """The dict of `predictive_scores` for targets `values` (C,) at `points` (C, d), from the state
+        (bark_leaf_posterior_predict_hip): "nlpd" and "mse" per forest (NaN for a forest of weight 0), and "nlpd_mixture" /
+        "mse_mixture" (with `return_values` "log_density" / "sq_err" per point) of the WEIGHTED mixture: the density
+        sum_b w_b N(y; mu_b, var_b) and the error against the weighted mean.  weights, observation, chunk, variant as in
+        `predict`.  On a freshly fitted state with equal weights and observation=False the result has the bits of
+        `predictive_scores(model, data, ...)` at the `chunk` of the fit."""
+        from ..fitting.mll import _y_vector
+
+        pts_d = self._predict_args(points, variant)
+        C = int(pts_d.shape[0])
+        n = int(values.numel()) if _is_torch(values) else int(np.size(values))
+        if n != C:
+            raise ValueError(f"the targets must have one entry per point ({C}), got {n}")
+        got = self._predict(pts_d, self._predict_weights(weights), observation, _y_vector(values, C), [], False, return_values, chunk,
+                            variant)
+        rows, mix = got["rows"], got["mix"]
+        out = {"nlpd": -rows[:, 0] / C, "mse": rows[:, 1] / C, "nlpd_mixture": -mix[0] / C, "mse_mixture": mix[1] / C}
+        if return_values:
+            out["log_density"], out["sq_err"] = got["values"][0], got["values"][1]
+        if _is_torch(points):
+            return out
+        return {k: (float(v.item()) if v.ndim == 0 else v.cpu().numpy()) for k, v in out.items()}
+
     def information_gain(self, query, target, targets, **kwargs):
         """-> gains (C,): what a value at query[c] tells about the minimum of the function target[c] lies on, whose draws are
         targets (B, S) — `bark_amd.optimizer.fidelity.information_gain(self, ...)`, which documents grid=, per_forest=, chunk=

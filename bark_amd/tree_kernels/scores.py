@@ -63,7 +63,7 @@ def _scores(model, data, points, y_points, domain, mode, return_values, chunk, v
 
 
 def predictive_scores(model, data, test_x, test_y, domain, *, return_values: bool = False, chunk: int | None = None,
-                      variant: str = "auto"):
+                      variant: str = "auto", posterior=None):
     """Scores of the forest samples' posteriors at C held-out points -> dict:
 
       "nlpd" (B,)      per forest b, -(1/C) sum_c log N(y_c; mu_bc, var_bc): the column of the reference's
@@ -84,7 +84,13 @@ def predictive_scores(model, data, test_x, test_y, domain, *, return_values: boo
 
     Torch test_x gives 0-d and 1-d device tensors; numpy test_x gives floats and numpy arrays.  ValueError when test_y
     does not have C entries, for shapes the entry point refuses and for an invalid categorical value; LinAlgError for a
-    forest whose leaf-space system is not positive definite; there is no CPU fallback (RuntimeError without a GPU)."""
+    forest whose leaf-space system is not positive definite; there is no CPU fallback (RuntimeError without a GPU).
+
+    posterior: a `LeafPosterior` (`fit_posterior`) to score instead of refitting; `model`, `data` and `domain` may then be
+    None.  The result is `posterior.scores(test_x, test_y, ...)`: the state as it is now, after every `observe_`, and the
+    mixture rows are those of its weighted mixture."""
+    if posterior is not None:
+        return posterior.scores(test_x, test_y, return_values=return_values, chunk=chunk, variant=variant)
     return _scores(model, data, test_x, test_y, domain, _lib.SCORE_HELDOUT, return_values, chunk, variant, _is_torch(test_x))
 
 

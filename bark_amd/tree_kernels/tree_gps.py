@@ -34,12 +34,21 @@ class BARKModel(NamedTuple):
     scale: np.ndarray
 
 
-def forest_predict(model, data, candidates, domain, diag: bool = True, method: str = "dense"):
+def forest_predict(model, data, candidates, domain, diag: bool = True, method: str = "dense", posterior=None):
     """tree_gps.py:80-113 -> (mu (B, C), var (B, C) or (B, C, C) if not diag); `domain` may be feat_types.
 
     method="dense" (default) follows the reference's computation (Gram, factorisation of the N x N matrix);
     method="leafspace" (diag only, <= 64 trees) evaluates the same posterior in closed form over the forest's
-    leaves: mu = c sum_{a in L(x)} w_a, var = (scale/m) sum_{a,b in L(x)} (M^-1)_ab — see include/bark_hip.h."""
+    leaves: mu = c sum_{a in L(x)} w_a, var = (scale/m) sum_{a,b in L(x)} (M^-1)_ab — see include/bark_hip.h.
+
+    posterior: a `LeafPosterior` (`fit_posterior`) to read instead of refitting: -> the "forest_mean" and "forest_var" of
+    `posterior.predict(candidates, per_forest=True, weights="equal")`, the state as it is now.  `model`, `data` and `domain`
+    may then be None; diag=True and the default method only (ValueError otherwise)."""
+    if posterior is not None:
+        if not diag or method != "dense":
+            raise ValueError("forest_predict(posterior=...) provides the diagonal posterior only, by the state's own method")
+        out = posterior.predict(candidates, per_forest=True, weights="equal")
+        return out["forest_mean"], out["forest_var"]
     forest, noise, scale = model
     train_x, train_y = data
     forest = np.asarray(forest)

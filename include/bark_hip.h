@@ -747,6 +747,66 @@ int bark_predictive_scores_hip(bark_ctx *ctx, const void *packed, const bark_pac
                                size_t workspace_bytes, int64_t Bc, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Predictions from a fitted posterior: what a surrogate is asked for first.  The state of bark_leaf_posterior_fit_hip, as
+ * bark_leaf_posterior_condition_hip / bark_leaf_posterior_observe_hip left it, read at C points (points (C, d) device) under
+ * the forest weights w_b: weights (device, (B,), non-negative, summing to 1: the caller normalises) or NULL for 1 / B each.
+ * Per forest b and point c, mu_bc and var_bc are the scan's mu_b(x) and var_b(x) above, formed the same way (the latent
+ * variance); with observation = 1, var_bc + s2_b (s2 = 1e-6 + noise): the predictive of an observation.  Outputs:
+ *   moments_out (2, C)       mean_c and var_c of the weighted mixture sum_b w_b N(mu_bc, var_bc), i.e. what the reference's
+ *                            mixture_of_gaussians_as_normal gives for equal weights, by West's weighted one-pass recurrence over
+ *                            the forests with w_b != 0 in forest order, from W = mean = S = V = 0:
+ *                                W += w;  delta = mu - mean;  mean += (w / W) delta;  S += (w delta)(mu - mean);  V += w var
+ *                            mean_c = mean, var_c = (V + S) / W: the law of total variance without the cancellation of
+ *                            sum w (var + mu^2) - mean^2 (y is not standardised here).  Every operation as written, rounded once.
+ *                            With one weight 1.0 and the others 0.0, mean_c = mu_bc and var_c = var_bc exactly.
+ *   forest_out (2, B, C)     mu_bc then var_bc, or NULL.
+ *   quantiles_out (Q, C)     for probs[q] = p the t with F_c(t) = sum_b w_b (1/2) erfc(-(t - mu_bc) / (sd_bc sqrt 2)) = p,
+ *                            sd_bc = sqrt(max(var_bc, 0)); a forest with sd_bc = 0 is a step at mu_bc.  probs and zscores are HOST
+ *                            arrays (Q,), zscores[q] = Phi^-1(probs[q]) (the caller's; it only places the bracket); both are read
+ *                            before the call returns.  Bracket: lo = min_b, hi = max_b of mu_bc + z sd_bc over the forests with
+ *                            w_b != 0; F(lo) >= p gives lo, F(hi) < p gives hi, so one live forest gives mu + z sd itself.  Inside,
+ *                            a Newton step on the mixture density, kept strictly inside a bracket that every evaluation tightens
+ *                            (bisection otherwise), until the step no longer moves t or no double lies between the ends.  F is
+ *                            summed over b = 0 .. B-1 from 0.0 and reads only the stored mu_bc, var_bc and w_b.
+ *   per_forest_out (B, 2), mixture_out (2,), values_out (2, C) or NULL: the predictive scores of y_points (device, (C,))
+ *                            as defined for bark_predictive_scores_hip, mode BARK_SCORE_HELDOUT, on mu_bc, var_bc above, with
+ *                            the weighted mixture:  log sum_b w_b exp l_bc  by the same online recurrence on l_bc + log w_b,
+ *                            result mx + log(se), and (y_c - mean_c)^2 with the recurrence's mean.  With weights == NULL the
+ *                            recurrence runs on l_bc, the results are mx + log(se / B) and (y_c - (sum_b mu_bc) / B)^2: the
+ *                            arithmetic of bark_predictive_scores_hip, whose bits a call on the freshly fitted state returns.
+ * Order (part of the contract): a point's leaves in code-bit order, forests b = 0 .. B-1 across chunks, the sums over points
+ *   by the tile tree and tile order of bark_predictive_scores_hip.  No float atomics.  No result depends on Bc or on the
+ *   variant, bit for bit, the quantiles included.
+ * A forest whose weight is exactly 0.0 is skipped whole and its status ignored, as in bark_acquisition_scan_fitted_weighted_hip;
+ *   its rows of forest_out and per_forest_out are NaN.  info_out[b]: the state's status, or -1 for an invalid categorical value
+ *   met by a walk of this call.  A non-zero entry of a forest of non-zero weight makes every entry of moments_out,
+ *   quantiles_out, mixture_out and values_out's sums NaN and its own rows of forest_out and per_forest_out NaN; the other rows
+ *   are what a call without that forest gives.  The weights are not read back: a negative or NaN weight gives a meaningless
+ *   result and no status.
+ * Limits, refused with BARK_ERR_ARG before any launch (and before the context is looked at): those of the fitted scan
+ *   (m <= 64, R <= 8192, 1 <= C <= 2^24, a state buffer of bark_leaf_posterior_bytes aligned to 256, variant = 1 only where the
+ *   LDS holds the table); 0 <= Q <= 16; a probs[q] outside (0, 1) or not finite, a zscores[q] not finite; probs or zscores NULL
+ *   with Q > 0; quantiles_out NULL with Q > 0 or given with Q = 0; moments_out or points NULL; y_points, per_forest_out and
+ *   mixture_out given in part; values_out without them; observation other than 0 or 1.  Nothing is rerouted.  The call only
+ *   enqueues: no allocation, no host synchronisation.
+ * workspace >= bark_leaf_posterior_predict_workspace_bytes(R, m, B, Bc, C, Q, want_forest, want_scores, variant) (pure host
+ *   code; 0 for a refused shape): the codes of one slab of at most 65536 points for Bc forests, the LDS image of Bc forests
+ *   when that variant runs, 4 C doubles and a flag word; with want_scores 3 C + 2 (B + 1) ceil(C / 256) doubles more; with
+ *   Q > 0 and no forest_out (want_forest = 0), 2 B min(C, 65536) doubles for mu_bc, var_bc of one slab.
+ * ------------------------------------------------------------------------------------- */
+size_t bark_leaf_posterior_predict_workspace_bytes(int64_t max_bits, int64_t m, int64_t B, int64_t Bc, int64_t C, int64_t Q,
+                                                   int want_forest, int want_scores, int variant);
+int bark_leaf_posterior_predict_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, int64_t d, const double *noise,
+                                    const double *scale, const void *state, size_t state_bytes, const double *points /* (C, d) */,
+                                    int64_t C, const double *weights /* (B,) or NULL */, int observation,
+                                    const double *y_points /* (C,) or NULL */, const double *probs /* host (Q,) */,
+                                    const double *zscores /* host (Q,) */, int64_t Q, int variant, double *moments_out /* (2, C) */,
+                                    double *forest_out /* (2, B, C) or NULL */, double *quantiles_out /* (Q, C) or NULL */,
+                                    double *per_forest_out /* (B, 2) or NULL */, double *mixture_out /* 2 or NULL */,
+                                    double *values_out /* (2, C) or NULL */, int32_t *info_out /* (B,) */, void *workspace,
+                                    size_t workspace_bytes, int64_t Bc, void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Woodbury / determinant-lemma updates — quick_inverse.py:13-33 (the per-tree step of the sampler,
  * bark_sampler.py:233-257).  With mul = -1 if `subtract` else +1:
  *   K_out         = K_inv - K_inv U (mul I + U' K_inv U)^-1 U' K_inv          (low_rank_inv_update)
