@@ -105,7 +105,7 @@ __global__ __launch_bounds__(ACQ_COND_THREADS) void acq_condition_kernel(const u
     }
 }
 
-// The same conditioning out of place, for a scan that starts from a fitted state it must not modify (leafsystem.hip,
+// The same conditioning out of place, for a scan that starts from a fitted state it must not modify (fitted.hip,
 // bark_acquisition_scan_fitted_hip): the first point reads `src` (the state's M^-1) and writes `dst` (scratch of the call),
 // the later points run in place on `dst`.  P >= 1.  Every product, sum and their order are acq_condition_kernel's, so `dst`
 // ends with the bits that kernel leaves in a matrix that started as `src`.  A forest whose sweep failed is copied as it is:

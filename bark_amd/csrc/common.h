@@ -10,6 +10,7 @@
 
 #include "../../include/bark_hip.h"
 #include "../../include/bark_hip_testing.h"
+#include "leaf_state.h"
 
 namespace bark {
 
@@ -125,6 +126,51 @@ int system_sweep_factor(SystemSweep *s);             // the identity columns whe
 int system_sweep_w(SystemSweep *s, double *w);       // after the factor, identity only: w = A^-1 v = V'z (bc, R)
 int system_sweep_minv(SystemSweep *s, double *Minv);  // ... and A^-1 = V'V (bc, R, R)
 
+// leafsystem.hip: what the stateless driver shares with the driver of the calls on a fitted state (fitted.hip)
+// dst[b] = src[b], b < n: status words from one place to another (a fitted state's and a call's info_out)
+int copy_info(const int32_t *src, int32_t *dst, int n, hipStream_t s);
+// an invalid categorical value met by a leaf walk since the context's flag was last read (ctx.hip): info[b] = -1, b < n
+int fault_info(const int32_t *fault, int32_t *info, int n, hipStream_t s);
+// The forests of a call and the chunk of them that is resident: LeafSystem and FittedCall are both one of these, and their
+// for_chunks set the chunk before the body runs.
+struct ForestChunk {
+    bark_ctx *ctx = nullptr;
+    hipStream_t caller = nullptr;
+    const void *packed = nullptr;
+    const bark_pack_info *info = nullptr;
+    int64_t d = 0, B = 0, Bc = 0;
+    int m = 0, R = 0, W = 0;
+    // the current chunk: its first forest, how many, and those forests as a pack of their own for the leaf walks
+    int64_t c0 = 0;
+    int bc = 0;
+    bark_pack_info sub{};
+    const char *packed_c = nullptr;
+
+    void set_chunk(int64_t c0_, int64_t n) {
+        c0 = c0_, bc = (int)n;
+        sub = *info;
+        sub.B = n;
+        packed_c = static_cast<const char *>(packed) + (size_t)c0 * m * info->stride * 16;
+    }
+    // one-hot codes (bc, W, npad of n) of n points under the chunk's forests
+    int walk(const double *points, int64_t n, uint32_t *codes) const {
+        return walk_one_hot(packed_c, &sub, points, n, d, W, codes, ctx->fault, caller);
+    }
+    // an invalid categorical value met by one of the chunk's walks goes into these bc status words
+    int take_fault(int32_t *chunk_info) const { return fault_info(ctx->fault, chunk_info, bc, caller); }
+};
+// The argument checks of an acquisition scan, stateless or from a state (`name`: the entry point's, for the messages), and
+// the variant that bark_acquisition_plan resolves for the forests' shape -> *var.
+int check_scan_args(const char *name, const bark_pack_info *info, const double *cand, int64_t C, const double *pending, int64_t P,
+                    const int64_t *skip_idx, int64_t n_skip, const double *targets, int64_t S, double kappa, int kind, int variant,
+                    const double *best_out, const int64_t *idx_out, int *var);
+// The chunk's part of an acquisition scan: the LDS image into `tab` when var == 1, then slab by slab of the C candidates the
+// walk into `ccodes` and acq_scan into acc (3, C).  w (bc, R) and Minv (bc, R, R) are the chunk's, already conditioned on any
+// pending points; noise, scale, targets (B, S) and weights (B,) or null are the call's, indexed from the chunk's first forest.
+int scan_chunk(const ForestChunk &ck, int var, int kind, const double *cand, int64_t C, const double *w, const double *Minv,
+               double *tab, uint32_t *ccodes, double *acc, const double *noise, const double *scale, double kappa,
+               const double *targets, int64_t S, const double *weights);
+
 // leafspace.hip: launchers of the leaf-space entry points (LeafSystem, leafsystem.hip)
 // leaf_inverse_kernel keeps the leaf lists of its 64 columns in dynamic LDS, m x 64 16-bit ids, so it takes forests of at
 // most 160 KiB / 128 B = 1280 trees
@@ -164,7 +210,6 @@ int sample_finish(const double *part, const int64_t *part_i, int nblk, int S, in
 // acquire.hip
 constexpr int ACQ_TILE = 256;               // points per workgroup of the scan and the score kernels, one per thread
 constexpr size_t ACQ_LDS_MAX = 160 * 1024;  // all of a CU's LDS: one workgroup per CU
-constexpr int ACQ_MAX_TREES = 64;
 int64_t acq_partials(int64_t C);
 // dynamic LDS of a scan / score launch: the tile's leaf lists and, with lds_table, the forest's image in front of them
 size_t scan_lds_bytes(int64_t R, int64_t m, bool lds_table);
@@ -193,7 +238,7 @@ int acq_finish(const double *acc, int64_t C, int B, double kappa, int kind, cons
                double *part_v, int64_t *part_i, const int32_t *info, const double *weights, double *best, int64_t *best_i,
                hipStream_t s);
 
-// scores.hip (launchers of bark_predictive_scores_hip, leafsystem.hip)
+// scores.hip (launchers of bark_predictive_scores_hip, leafsystem.hip; predict's scores, fitted.hip, end in score_forests too)
 // n points of one slab, whose first tile is tile0 of the call's `tiles`, against the bc forests of the chunk: the mixture's
 // running state per point in the slab's part of acc (3, C; row stride astride) and one partial pair per (forest, tile) in
 // fpart (bc, tiles, 2).  variant as acq_scan; mode: BARK_SCORE_*; info: the chunk's sweep status; yp: the slab's targets
@@ -206,7 +251,7 @@ int score_forests(const double *fpart, int tiles, int bc, double *rows, hipStrea
 int score_finish(const double *acc, int64_t C, int B, const double *yp, double *values_out, double *mpart, const int32_t *info,
                  double *per_forest_out, double *mixture_out, hipStream_t s);
 
-// predict.hip (launchers of bark_leaf_posterior_predict_hip, leafsystem.hip)
+// predict.hip (launchers of bark_leaf_posterior_predict_hip, fitted.hip)
 // n points of one slab against the bc forests of the chunk, as score_scan: West's recurrence per point in the slab's part of
 // acc (4, C; row stride astride).  weights: the chunk's rows of the normalised weights, or null (every forest weighs wq);
 // info: the chunk's status in the state; fmu / fvar: the chunk's first rows of the per-forest output (row stride fstride) or
@@ -230,7 +275,7 @@ int predict_score_finish(const double *acc, const double *sacc, int64_t C, int B
                          double *values_out, double *mpart, const int32_t *info, const int32_t *flag, double *per_forest_out,
                          double *mixture_out, hipStream_t s);
 
-// fidelity.hip (launchers of bark_fidelity_gain_fitted_hip, leafsystem.hip)
+// fidelity.hip (launchers of bark_fidelity_gain_fitted_hip, fitted.hip)
 constexpr int FID_MOMENTS = 6;  // doubles per (forest, candidate) between the moments and the quadrature kernel
 size_t fidelity_moments_lds_bytes(int64_t m);
 // n pairs (query, target) whose codes are qcodes / tcodes (bc, W, cpad) against the bc forests of the chunk: mom
@@ -257,7 +302,6 @@ constexpr int TILE = 128;  // Cholesky block size == MFMA tile edge per workgrou
 constexpr int MAX_LEAF_WORDS = 112;  // leaf-code dwords per point the Gram kernels can stage in LDS
 
 inline int64_t round_up(int64_t x, int64_t q) { return (x + q - 1) / q * q; }
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }  // workspace areas start on 256-byte boundaries
 
 // Number of differing bytes of two dwords that each pack 4 dense leaf ids (one tree per byte): a tree pair
 // agrees iff its byte of a ^ b is zero.  Ids < 128 keep bit 7 clear, so `x + 0x7f7f7f7f` cannot carry

@@ -10,7 +10,7 @@
 //   bark_path_scan_hip              f[p][x] = sum_t W[p][col_t(x)] over candidates, trees strictly in the order t = 0..m-1; FULL,
 //                                   or MAX / MIN through fixed-order partials per workgroup and sample.hip's finish kernel.
 // The path list is a host array: the launches are planned from it, and a table of its runs (one per forest that occurs) goes
-// to the device through the context's staging page.
+// to the device through the context's staging page.  The state is read where posterior_state (leaf_state.h) says its areas are.
 #include <cmath>
 #include <cstring>
 
@@ -278,16 +278,6 @@ __global__ void path_status_kernel(const int32_t *__restrict__ run_b, const int3
 }
 
 // ---- host ----
-struct Carve {
-    char *base;
-    size_t o = 0;
-    template <class T> T *take(size_t n) {
-        T *p = base ? reinterpret_cast<T *>(base + o) : nullptr;
-        o = align256(o + n * sizeof(T));
-        return p;
-    }
-};
-
 bool paths_shape_ok(int64_t R, int64_t m) { return R >= 1 && R <= PATHS_MAX_LEAVES && m >= 1 && m <= PS_MAX_TREES; }
 int64_t factors_resident(int64_t R) {
     const int64_t k = (int64_t)(PATHS_G_BYTES / ((size_t)R * R * sizeof(double)));
@@ -395,9 +385,8 @@ int bark_leaf_posterior_paths_hip(bark_ctx *ctx, const bark_pack_info *info, con
     if (B < 1 || P < 1 || P > PATHS_MAX)
         return fail(BARK_ERR_ARG, "%s: 1 to %lld paths per call and B >= 1 (got P = %lld, B = %lld)", name, (long long)PATHS_MAX,
                     (long long)P, (long long)B);
-    const size_t need_state = bark_leaf_posterior_bytes(R, m, B);
-    if (need_state == 0 || state_bytes < need_state)
-        return fail(BARK_ERR_ARG, "%s: state buffer too small: %zu < %zu bytes", name, state_bytes, need_state);
+    const PosteriorState st = posterior_state(const_cast<void *>(state), R, B);  // read only; its shape is inside the plan's limits
+    if (state_bytes < st.total) return fail(BARK_ERR_ARG, "%s: state buffer too small: %zu < %zu bytes", name, state_bytes, st.total);
     if ((reinterpret_cast<uintptr_t>(state) | reinterpret_cast<uintptr_t>(workspace)) & 255)
         return fail(BARK_ERR_ARG, "%s: state and workspace must be 256-byte aligned", name);
     std::vector<int32_t> table((size_t)3 * P + 1);
@@ -413,12 +402,8 @@ int bark_leaf_posterior_paths_hip(bark_ctx *ctx, const bark_pack_info *info, con
     hipStream_t s = static_cast<hipStream_t>(stream_);
     if ((rc = bark_ctx_upload(ctx, a.table, table.data(), table.size() * sizeof(int32_t), stream_))) return rc;
     const int32_t *draw = a.table, *run_b = a.table + P, *run_p0 = run_b + P;
-    // the state's areas: M^-1 (B, R, R), w (B, R), status (B), each 256-byte aligned (bark_leaf_posterior_bytes)
-    const char *st = static_cast<const char *>(state);
-    const double *Minv = reinterpret_cast<const double *>(st);
-    const double *wvec = reinterpret_cast<const double *>(st + align256((size_t)B * R * R * 8));
-    const int32_t *st_info = reinterpret_cast<const int32_t *>(st + align256((size_t)B * R * R * 8) + align256((size_t)B * R * 8));
-    hipLaunchKernelGGL(paths_info_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, st_info, info_out, (int)B);
+    const double *Minv = st.Minv, *wvec = st.w;
+    hipLaunchKernelGGL(paths_info_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, s, (const int32_t *)st.info, info_out, (int)B);
     BARK_LAUNCH_CHECK();
     if (!eps) {
         hipLaunchKernelGGL(paths_normals_kernel, dim3((unsigned)(((R + 1) / 2 + 127) / 128), (unsigned)P), dim3(128), 0, s, run_b, run_p0,

@@ -1,7 +1,8 @@
 // Importance weights of the forest samples of a fitted posterior (contract in include/bark_hip.h): the weight update
 // (forest_weights_kernel, bark_forest_weights_hip) and the gather of state rows that a subset or a resampling copies
-// (posterior_gather_kernel, bark_leaf_posterior_gather_hip).  Neither kernel uses an atomic: the update is one workgroup
-// with plain loads, wave shuffles and one LDS stage; the gather writes every output element from exactly one thread.
+// (posterior_gather_kernel, bark_leaf_posterior_gather_hip; both states are laid out by posterior_state, leaf_state.h).
+// Neither kernel uses an atomic: the update is one workgroup with plain loads, wave shuffles and one LDS stage; the gather
+// writes every output element from exactly one thread.
 #include <cmath>
 #include <vector>
 
@@ -120,25 +121,6 @@ __global__ __launch_bounds__(GATHER_THREADS) void posterior_gather_kernel(const 
     }
 }
 
-// the layout of a fitted state (leafsystem.hip, posterior_state): M^-1, w and the status, each area 256-byte aligned
-struct GatherState {
-    double *Minv, *w;
-    int32_t *info;
-    size_t total;
-};
-GatherState gather_state(void *base, int64_t R, int64_t B) {
-    char *p = static_cast<char *>(base);
-    GatherState st;
-    size_t o = 0;
-    st.Minv = reinterpret_cast<double *>(p + o);
-    o = align256(o + (size_t)B * R * R * sizeof(double));
-    st.w = reinterpret_cast<double *>(p + o);
-    o = align256(o + (size_t)B * R * sizeof(double));
-    st.info = reinterpret_cast<int32_t *>(p + o);
-    st.total = align256(o + (size_t)B * sizeof(int32_t));
-    return st;
-}
-
 }  // namespace
 }  // namespace bark
 
@@ -168,7 +150,7 @@ int bark_leaf_posterior_gather_hip(const void *state_in, int64_t B_in, int64_t R
                     (long long)R, (long long)n);
     if ((reinterpret_cast<uintptr_t>(state_in) | reinterpret_cast<uintptr_t>(state_out)) & 255)
         return fail(BARK_ERR_ARG, "%s: the states must be 256-byte aligned", name);
-    const GatherState in = gather_state(const_cast<void *>(state_in), R, B_in), out = gather_state(state_out, R, n);
+    const PosteriorState in = posterior_state(const_cast<void *>(state_in), R, B_in), out = posterior_state(state_out, R, n);
     const uintptr_t a0 = reinterpret_cast<uintptr_t>(state_in), b0 = reinterpret_cast<uintptr_t>(state_out);
     if (a0 < b0 + out.total && b0 < a0 + in.total) return fail(BARK_ERR_ARG, "%s: state_in and state_out overlap", name);
     hipStream_t s = static_cast<hipStream_t>(stream);
