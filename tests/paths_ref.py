@@ -75,3 +75,77 @@ def first_argmin(f, maximise=False):
     """(values, indices) per row, the lowest index among equals."""
     idx = np.argmax(f, axis=1) if maximise else np.argmin(f, axis=1)  # numpy returns the first occurrence
     return f[np.arange(f.shape[0]), idx], idx.astype(np.int64)
+
+
+# ---- where the host drivers cut their work, read off the library's own byte queries (no GPU) ----
+MAX_PATHS = 4096  # paths per C call
+
+
+def resident_factors(lib, R, m=1):
+    """Factors bark_leaf_posterior_paths_hip keeps in its workspace at a time, at most 4096: with 4096 forests and 4096
+    paths the workspace is the run table (3 P + 1 ints) and min(4096, resident) matrices of R x R doubles, each area
+    rounded up to 256 bytes."""
+    total = int(lib.bark_leaf_posterior_paths_workspace_bytes(R, m, MAX_PATHS, MAX_PATHS, 0))
+    area = total - align256(4 * (3 * MAX_PATHS + 1))
+    k = area // (8 * R * R)
+    assert total > 0 and align256(8 * k * R * R) == area, (R, total)
+    return k
+
+
+def scan_walk(lib, R, m, C):
+    """Forests bark_path_scan_hip walks together over C candidates: a FULL scan of one path keeps the run table (3 ints),
+    a flag and the one-hot codes of `walk` forests, ceil(R / 32) words for each candidate of a slab (at most 65 536,
+    padded to 128)."""
+    total = int(lib.bark_path_scan_workspace_bytes(R, m, 1, C, 0))
+    words, cpad = -(-R // 32), -(-min(C, 65536) // 128) * 128
+    walk, rest = divmod(total - 512, 4 * words * cpad)
+    assert total > 0 and rest == 0, (R, C, total)
+    return walk
+
+
+def smallest_candidates_below(lib, R, m, forests):
+    """The smallest candidate count, a multiple of 128 as the padded slab is, at which fewer than `forests` forests are
+    walked together; every count from 127 below it up to a slab gives the same walk."""
+    for C in range(128, 65536 + 1, 128):
+        if scan_walk(lib, R, m, C) < forests:
+            return C
+    raise AssertionError(f"{forests} forests of {R} leaves are walked together at every candidate count")
+
+
+def walk_chunks(sorted_forest, walk):
+    """[(first forest, forests)] of the leaf walks bark_path_scan_hip makes for a sorted path list: the forests that occur,
+    cut where the next one is not the successor of the last and after `walk` of them."""
+    runs = np.unique(np.asarray(sorted_forest))
+    chunks, r0 = [], 0
+    while r0 < len(runs):
+        n = 1
+        while r0 + n < len(runs) and n < walk and runs[r0 + n] == runs[r0] + n:
+            n += 1
+        chunks.append((int(runs[r0]), n))
+        r0 += n
+    return chunks
+
+
+def call_splits(sorted_forest):
+    """[(first path, paths)] of the C calls Python makes for a sorted path list of any length."""
+    P = len(sorted_forest)
+    return [(p0, min(MAX_PATHS, P - p0)) for p0 in range(0, P, MAX_PATHS)]
+
+
+def meets_invalid_categorical(F_b, ft, x):
+    """Whether the device walk of row x through forest F_b (m, node_limit) sets the fault flag: some tree's path from
+    the root comes to a categorical split whose feature value truncates to something negative or not finite
+    (walk_tree in common.h; such a value goes right and the walk continues)."""
+    for tree in F_b:
+        node = tree[0]
+        while not node["is_leaf"]:
+            f = int(node["feature_idx"])
+            if ft[f] == 0:
+                xt = np.trunc(x[f])
+                if not (xt >= 0.0 and xt < np.inf):
+                    return True
+                left = bool((int(node["threshold"]) >> int(xt)) & 1) if xt < 32 else False
+            else:
+                left = x[f] <= node["threshold"]
+            node = tree[int(node["left"] if left else node["right"])]
+    return False

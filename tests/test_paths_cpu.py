@@ -97,6 +97,88 @@ def test_plan_and_workspace_queries_and_refusals():
     assert {"bark_leaf_posterior_paths_hip", "bark_path_scan_hip", "bark_leaf_posterior_paths_plan"} <= set(_lib.SIGNATURES)
 
 
+def test_the_cuts_of_the_host_drivers_lie_where_the_gpu_tests_cross_them():
+    """tests/test_gpu_paths_chunks.py picks its shapes to cross these three; read off the byte queries as it reads them."""
+    lib = _lib.lib()
+    # resident factors: floor(256 MiB / 8 R^2)
+    assert paths_ref.resident_factors(lib, 2048, 64) == 8 and paths_ref.resident_factors(lib, 2048) == 8
+    assert paths_ref.resident_factors(lib, 1449) == 15 and paths_ref.resident_factors(lib, 1448) == 16
+    assert paths_ref.resident_factors(lib, 2047) == 8 and paths_ref.resident_factors(lib, 1931) == 8 and paths_ref.resident_factors(lib, 1930) == 9
+    # forests per leaf walk: 16 while their codes of one slab fit 64 MiB
+    for R, m, C in ((11, 3, 300), (11, 3, 1), (65, 33, 300), (385, 4, 65537), (2048, 64, 128), (2048, 64, 16384)):
+        assert paths_ref.scan_walk(lib, R, m, C) == 16, (R, C)
+    assert paths_ref.scan_walk(lib, 2048, 64, 16385) == 15 and paths_ref.scan_walk(lib, 2048, 64, 65536) == 4
+    # the leaf-limit fixture: 9 forests of 2048 leaves are first cut at 64 MiB / (64 words x 4 bytes x 9) = 29 127.1 candidates
+    C = paths_ref.smallest_candidates_below(lib, 2048, 64, 9)
+    assert C == 29184 and paths_ref.scan_walk(lib, 2048, 64, C - 37) == 8 and paths_ref.scan_walk(lib, 2048, 64, C - 128) == 9
+    # the leaf walks of a sorted list: cut at a missing forest and after `walk` consecutive ones
+    full = list(range(17)) + [17] * 17 + [18]
+    assert paths_ref.walk_chunks(full, 16) == [(0, 16), (16, 3)] and paths_ref.walk_chunks(full, 8) == [(0, 8), (8, 8), (16, 3)]
+    assert paths_ref.walk_chunks(list(range(7)) + list(range(8, 19)), 16) == [(0, 7), (8, 11)]
+    assert paths_ref.walk_chunks([17, 17, 18], 16) == [(17, 2)] and paths_ref.walk_chunks([3], 1) == [(3, 1)]
+    assert paths_ref.walk_chunks(list(range(8)) + [8] * 17, 8) == [(0, 8), (8, 1)]
+    assert paths_ref.call_splits(np.zeros(4096)) == [(0, 4096)] and paths_ref.call_splits(np.zeros(4100)) == [(0, 4096), (4096, 4)]
+    assert paths_ref.MAX_PATHS == 4096
+    from bark_amd.tree_kernels import posterior
+
+    assert posterior.MAX_PATHS_PER_CALL == paths_ref.MAX_PATHS
+    assert lib.bark_path_scan_workspace_bytes(11, 3, 4096, 64, 0) > 0 == lib.bark_path_scan_workspace_bytes(11, 3, 4097, 64, 0)
+
+
+def test_path_list_across_the_split_at_4096():
+    """The 4100-entry list of the GPU test: the draw number counts the earlier entries of the same forest in the caller's
+    order whichever side of the split at 4096 they fall on, and `order` is the stable sort."""
+    counts = (1500, 2598, 2)
+    forests = np.random.default_rng(8).permutation(np.repeat(np.arange(3), counts))
+    forest, draw, order = path_list(forests, 3)
+    assert forest.tolist() == forests.tolist() and len(order) == 4100
+    seen = [0, 0, 0]
+    for i, b in enumerate(forests):  # by hand
+        assert draw[i] == seen[b]
+        seen[b] += 1
+    assert tuple(seen) == counts
+    srt = forest[order]
+    assert (np.diff(srt) >= 0).all() and np.array_equal(order, np.argsort(forests, kind="stable"))
+    for b in range(3):  # stable: inside a forest's run the caller's positions rise, so the draws are 0, 1, 2, ...
+        run = order[srt == b]
+        assert (np.diff(run) > 0).all() and draw[run].tolist() == list(range(counts[b]))
+    # forest 1 straddles the split: the second call starts with its draws 2596 and 2597
+    assert srt[4095] == srt[4096] == 1 and draw[order][4094:].tolist() == [2594, 2595, 2596, 2597, 0, 1]
+    assert paths_ref.call_splits(srt) == [(0, 4096), (4096, 4)]
+
+
+def test_the_walk_that_sets_the_fault_flag():
+    """paths_ref.meets_invalid_categorical against the oracle's walk, which refuses the same rows as a whole."""
+    from oracle import oracle as orc
+
+    kw = dict(d_cont=2, n_int=1, n_cat=1)
+    X, y, bounds, ft = synthetic.mixed_problem(24, seed=35, **kw)
+    F = synthetic.sample_prior_forests(19, 3, bounds, ft, seed=36)
+    cand = synthetic.mixed_problem(40, seed=36, **kw)[0]
+    cat = int(np.flatnonzero(ft == 0)[0])
+    met = 0
+    for x in cand:
+        assert not any(paths_ref.meets_invalid_categorical(F[b], ft, x) for b in range(19))
+        for value in (-1.0, np.nan, np.inf, -0.5):
+            bad = x.copy()
+            bad[cat] = value
+            for b in (0, 5, 17):
+                meets = paths_ref.meets_invalid_categorical(F[b], ft, bad)
+                if value == -0.5:  # truncates to -0.0: category 0, valid
+                    assert not meets
+                if value == -1.0:
+                    met += meets
+                    try:
+                        leaves = orc.pass_through_forest(F[b], bad[None], ft)
+                        refused = False
+                    except ValueError:
+                        refused = True
+                    assert refused == meets
+                    if not meets:  # the feature was never tested on the way down: the leaves are those of the valid row
+                        assert np.array_equal(leaves, orc.pass_through_forest(F[b], x[None], ft))
+    assert 0 < met < 3 * len(cand)
+
+
 def test_reference_identity_on_the_test_inputs():
     """G G' = M^-1 for the restatement's factor, in float64 and in longdouble, on the shape of the GPU tests (B = 3, m = 5,
     N = 40, d = 4 with one categorical and one integer feature)."""
