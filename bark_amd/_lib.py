@@ -174,6 +174,9 @@ SIGNATURES = {
     "bark_leaf_posterior_predict_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64, i64, i64, ci, ci, ci]),
     "bark_leaf_posterior_predict_hip": (ci, [vp, vp, ctypes.POINTER(PackInfo), i64, vp, vp, vp, ctypes.c_size_t, vp, i64, vp, ci, vp, vp,
                                              vp, i64, ci, vp, vp, vp, vp, vp, vp, vp, vp, ctypes.c_size_t, i64, vp]),
+    "bark_leaf_posterior_covariance_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64, i64, i64, ci, ci, ci, ci]),
+    "bark_leaf_posterior_covariance_hip": (ci, [vp, vp, ctypes.POINTER(PackInfo), i64, vp, vp, vp, ctypes.c_size_t, vp, i64, vp, i64,
+                                                vp, ci, ci, vp, vp, vp, vp, ctypes.c_size_t, i64, vp]),
     "bark_forest_weights_hip": (ci,[vp, vp, vp, i64, vp, vp, vp, vp]),
     "bark_leaf_posterior_gather_hip": (ci, [vp, i64, i64, vp, i64, vp, vp]),
     "bark_leaf_posterior_condition_workspace_bytes": (ctypes.c_size_t, [i64, i64, i64, i64]),

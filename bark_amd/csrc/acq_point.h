@@ -18,7 +18,9 @@ __device__ __forceinline__ void stage_table(const double *__restrict__ tab, int 
 }
 
 // Leaves of point c under forest b from its one-hot code (ccodes (bc, W, cpad)), in code-bit order (tree order), into
-// idx[k * ACQ_TILE]; returns their number, which the caller clamps to m (only the first m are stored).
+// idx[k * STRIDE]; returns their number, which the caller clamps to m (only the first m are stored).  STRIDE: the lists of
+// the workgroup side by side, ACQ_TILE for the one-thread-per-point kernels; covariance.hip holds two shorter sets of lists.
+template <int STRIDE = ACQ_TILE>
 __device__ __forceinline__ int point_leaves(const uint32_t *__restrict__ ccodes, int W, int cpad, int b, int c, int m, int R,
                                             unsigned short *idx) {
     int cnt = 0;
@@ -31,7 +33,7 @@ __device__ __forceinline__ int point_leaves(const uint32_t *__restrict__ ccodes,
             uint32_t bits = word[u];
             while (bits) {  // bits in increasing order: tree order
                 const int a = 32 * (w0 + u) + __builtin_ctz(bits);
-                if (cnt < m) idx[cnt * ACQ_TILE] = (unsigned short)(a < R ? a : R - 1);
+                if (cnt < m) idx[cnt * STRIDE] = (unsigned short)(a < R ? a : R - 1);
                 bits &= bits - 1;
                 ++cnt;
             }

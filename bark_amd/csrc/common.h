@@ -275,6 +275,24 @@ int predict_score_finish(const double *acc, const double *sacc, int64_t C, int B
                          double *values_out, double *mpart, const int32_t *info, const int32_t *flag, double *per_forest_out,
                          double *mixture_out, hipStream_t s);
 
+// covariance.hip (launchers of bark_leaf_posterior_covariance_hip, fitted.hip)
+// cov_b = (scale_b / m) Z_1 M_b^-1 Z_2' of the chunk's forests into out (bc, C1, C2), from the codes of the C1 row points and
+// of the C2 column points (symmetric: the same codes; then only the tiles of one triangle are computed and every entry is
+// stored twice).  variant: 1 keeps a tile's T in LDS, 2 reads M^-1 from global memory (bark_acquisition_plan resolves it: a
+// table that fits the scan's LDS gives a T tile that fits half a CU's).  weights: the chunk's rows or null; a forest of weight 0
+// is left alone.  observation: s2_b onto the diagonal
+int cov_tiles(int variant, const uint32_t *codes1, int cpad1, int C1, const uint32_t *codes2, int cpad2, int C2, int W, const double *Minv,
+              int R, const double *noise, const double *scale, int m, int bc, const double *weights, int symmetric, int observation,
+              double *out, hipStream_t s);
+// the chunk's forests of non-zero weight, in order, onto the running sum mix (C1, C2) (first: it starts at zero):
+// w_b (cov_b + (mu1_b - mean1)(mu2_b - mean2)'), with cov (bc, C1, C2), mu1 (bc, C1) and mu2 (bc, C2) the chunk's rows
+int cov_accumulate(const double *cov, int64_t C1, int64_t C2, const double *mu1, const double *mean1, const double *mu2,
+                   const double *mean2, const double *weights, double wq, int bc, int first, double *mix, hipStream_t s);
+// after the last chunk: mix (or null) divided by *Wsum, NaN under the flag; NaN blocks of forest_out (B, C1, C2) or null for
+// the forests of weight 0 or with a non-zero status
+int cov_finish(double *mix, int64_t C1, int64_t C2, const double *Wsum, const int32_t *flag, const int32_t *info, const double *weights,
+               int B, double *forest_out, hipStream_t s);
+
 // fidelity.hip (launchers of bark_fidelity_gain_fitted_hip, fitted.hip)
 constexpr int FID_MOMENTS = 6;  // doubles per (forest, candidate) between the moments and the quadrature kernel
 size_t fidelity_moments_lds_bytes(int64_t m);

@@ -1,11 +1,11 @@
 // Host side of the calls that start from a fitted leaf-space posterior (include/bark_hip.h): the acquisition scan from the
-// state, plain and weighted, the fidelity gain, condition / observe, which change the state in place, and predict.  The state
-// (PosteriorState, leaf_state.h) is written by bark_leaf_posterior_fit_hip, a LeafSystem call (leafsystem.hip); these calls
-// factorise nothing, so they have no sweep and no LeafSystem.  FittedCall is what they share: the checks, the state's areas,
-// the chunk loop and its per-chunk steps.  An entry point checks its own arguments, opens the call, carves its workspace and
-// hands for_chunks a body.
-// This unit defines no kernel: the scan's are in acquire.hip, the others in fidelity.hip, predict.hip and scores.hip, and the
-// two that move status words in leafsystem.hip.
+// state, plain and weighted, the fidelity gain, condition / observe, which change the state in place, predict and the joint
+// covariance.  The state (PosteriorState, leaf_state.h) is written by bark_leaf_posterior_fit_hip, a LeafSystem call
+// (leafsystem.hip); these calls factorise nothing, so they have no sweep and no LeafSystem.  FittedCall is what they share: the
+// checks, the state's areas, the chunk loop and its per-chunk steps.  An entry point checks its own arguments, opens the call,
+// carves its workspace and hands for_chunks a body.
+// This unit defines no kernel: the scan's are in acquire.hip, the others in fidelity.hip, predict.hip, covariance.hip and
+// scores.hip, and the two that move status words in leafsystem.hip.
 #include <cmath>
 
 #include "common.h"
@@ -180,6 +180,42 @@ PredictAreas predict_areas(void *workspace, int64_t R, int64_t B, int64_t Bc, in
     a.total = cv.o;
     return a;
 }
+
+// ---- joint covariance from the state (kernels in covariance.hip) ----
+
+constexpr int64_t COV_MAX_POINTS = ACQ_SLAB;  // points per side: one slab of codes
+
+// The workspace of the covariance call: the codes of the C1 row points and, unless the call is symmetric, of the C2 column
+// points for Bc forests; for the mixture the (4, C) recurrence state and mu_b / var_b (2, B, C) of each side (predict_scan's)
+// and the flag word; and the blocks of one chunk (Bc, C1, C2) when the caller takes no forest_out to hold them.
+struct CovAreas {
+    int64_t cpad1, cpad2;
+    uint32_t *codes1, *codes2;
+    double *acc1, *acc2, *fm1, *fm2, *cov;
+    int32_t *flag;
+    size_t total;
+};
+CovAreas cov_areas(void *workspace, int64_t R, int64_t B, int64_t Bc, int64_t C1, int64_t C2, bool symmetric, bool want_forest,
+                   bool want_mixture) {
+    CovAreas a;
+    const int64_t W = (R + 31) / 32;
+    a.cpad1 = round_up(C1, TILE);
+    a.cpad2 = symmetric ? a.cpad1 : round_up(C2, TILE);
+    const size_t nb = (size_t)Bc;
+    Carve cv{static_cast<char *>(workspace)};
+    a.codes1 = cv.take<uint32_t>(nb * W * a.cpad1);
+    a.codes2 = cv.take<uint32_t>(symmetric ? 0 : nb * W * a.cpad2);
+    a.acc1 = cv.take<double>(want_mixture ? (size_t)4 * C1 : 0);
+    a.acc2 = cv.take<double>(want_mixture && !symmetric ? (size_t)4 * C2 : 0);
+    a.fm1 = cv.take<double>(want_mixture ? (size_t)2 * B * C1 : 0);
+    a.fm2 = cv.take<double>(want_mixture && !symmetric ? (size_t)2 * B * C2 : 0);
+    a.flag = cv.take<int32_t>(1);
+    a.cov = cv.take<double>(want_forest ? 0 : nb * C1 * C2);
+    a.total = cv.o;
+    if (symmetric) a.codes2 = a.codes1, a.acc2 = a.acc1, a.fm2 = a.fm1;
+    return a;
+}
+bool cov_points_ok(int64_t C) { return C >= 1 && C <= COV_MAX_POINTS; }
 
 }  // namespace
 }  // namespace bark
@@ -451,6 +487,92 @@ int bark_leaf_posterior_predict_hip(bark_ctx *ctx, const void *packed, const bar
         if (rc) return rc;
     }
     return predict_finish(a.acc, C, B, info_out, a.flag, moments_out, forest_out, quantiles_out, (int)Q, fc.caller);
+}
+
+size_t bark_leaf_posterior_covariance_workspace_bytes(int64_t max_bits, int64_t m, int64_t B, int64_t Bc, int64_t C1, int64_t C2,
+                                                      int symmetric, int want_forest, int want_mixture, int variant) {
+    if (symmetric) C2 = C1;
+    if (B < 1 || Bc < 1 || !cov_points_ok(C1) || !cov_points_ok(C2) || (!want_forest && !want_mixture) ||
+        bark_acquisition_plan(max_bits, m, variant, nullptr, nullptr)) {
+        error_buffer()[0] = 0;  // a query reports through its value only
+        return 0;
+    }
+    if (Bc > B) Bc = B;
+    if (Bc > 65535) Bc = 65535;
+    return cov_areas(nullptr, max_bits, B, Bc, C1, C2, symmetric != 0, want_forest != 0, want_mixture != 0).total;
+}
+
+// With a mixture, first chunk by chunk the walks and predict_scan_kernel at the row and the column points: the means of the
+// mixture, its W and mu_b of every forest.  Then chunk by chunk the walks, the chunk's blocks (into forest_out, or into the
+// workspace) and their sum onto mixture_out in forest order; the finish after the last chunk.  The state is only read.  Every
+// argument, the state's size and alignment included, is checked before the context is, so a refusal needs no device.
+int bark_leaf_posterior_covariance_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, int64_t d, const double *noise,
+                                       const double *scale, const void *state, size_t state_bytes, const double *x1, int64_t C1,
+                                       const double *x2, int64_t C2, const double *weights, int observation, int variant,
+                                       double *forest_out, double *mixture_out, int32_t *info_out, void *workspace,
+                                       size_t workspace_bytes, int64_t Bc, void *stream_) {
+    static const char *name = "bark_leaf_posterior_covariance_hip";
+    error_buffer()[0] = 0;
+    if (!info || !x1 || !state) return fail(BARK_ERR_ARG, "%s: null argument", name);
+    const bool symmetric = x2 == nullptr;
+    if (symmetric) C2 = C1;
+    if (!cov_points_ok(C1) || !cov_points_ok(C2))
+        return fail(BARK_ERR_ARG, "%s: between 1 and %lld points per side (got %lld and %lld)", name, (long long)COV_MAX_POINTS,
+                    (long long)C1, (long long)C2);
+    if (!forest_out && !mixture_out) return fail(BARK_ERR_ARG, "%s: forest_out, mixture_out or both must be given", name);
+    if (observation != 0 && observation != 1) return fail(BARK_ERR_ARG, "%s: observation is 0 or 1 (got %d)", name, observation);
+    if (observation && !symmetric)
+        return fail(BARK_ERR_ARG, "%s: observation noise belongs to the symmetric call (x2 == NULL): two evaluations share none", name);
+    int var = 0, rc;
+    if ((rc = bark_acquisition_plan(info->max_bits, info->m, variant, &var, nullptr))) return rc;
+    if (info->B < 1) return fail(BARK_ERR_ARG, "%s: bad shape B=%lld", name, (long long)info->B);
+    if ((rc = FittedCall::check_state(name, info, state, state_bytes))) return rc;
+    FittedCall fc;
+    if ((rc = fc.open(name, ctx, packed, info, d, noise, scale, state, state_bytes, info_out, workspace, Bc, stream_))) return rc;
+    const int R = fc.R, B = (int)fc.B;
+    const bool mix = mixture_out != nullptr;
+    const CovAreas a = cov_areas(workspace, R, B, fc.Bc, C1, C2, symmetric, forest_out != nullptr, mix);
+    if (workspace_bytes < a.total) return fail(BARK_ERR_WORKSPACE, "workspace too small: %zu < %zu bytes", workspace_bytes, a.total);
+    const double wq = 1.0 / (double)B;
+    const size_t n12 = (size_t)C1 * C2;
+    if ((rc = fc.copy_status(info_out))) return rc;
+    if (mix) {
+        // predict's recurrence at both sides, M^-1 read from global memory (its bits do not depend on its variant): rows W and
+        // mean of acc, mu_b in the first B rows of fm
+        rc = fc.for_chunks([&]() -> int {
+            const size_t c0 = (size_t)fc.c0;
+            const double *wt = weights ? weights + c0 : nullptr;
+            int r;
+            if ((r = fc.walk(x1, C1, a.codes1))) return r;
+            r = predict_scan(2, false, a.codes1, fc.W, (int)a.cpad1, (int)C1, fc.w(), fc.Minv(), nullptr, R, fc.noise_c(), fc.scale_c(), fc.m,
+                             fc.bc, fc.status(), wt, wq, 0, nullptr, c0 == 0, a.acc1, (size_t)C1, nullptr, a.fm1 + c0 * C1,
+                             a.fm1 + ((size_t)B + c0) * C1, (size_t)C1, nullptr, 0, 0, fc.caller);
+            if (r || symmetric) return r;
+            if ((r = fc.walk(x2, C2, a.codes2))) return r;
+            return predict_scan(2, false, a.codes2, fc.W, (int)a.cpad2, (int)C2, fc.w(), fc.Minv(), nullptr, R, fc.noise_c(), fc.scale_c(),
+                                fc.m, fc.bc, fc.status(), wt, wq, 0, nullptr, c0 == 0, a.acc2, (size_t)C2, nullptr, a.fm2 + c0 * C2,
+                                a.fm2 + ((size_t)B + c0) * C2, (size_t)C2, nullptr, 0, 0, fc.caller);
+        });
+        if (rc) return rc;
+    }
+    rc = fc.for_chunks([&]() -> int {
+        const size_t c0 = (size_t)fc.c0;
+        const double *wt = weights ? weights + c0 : nullptr;
+        double *blocks = forest_out ? forest_out + c0 * n12 : a.cov;  // (bc, C1, C2) either way
+        int r;
+        if ((r = fc.walk(x1, C1, a.codes1))) return r;
+        if (!symmetric && (r = fc.walk(x2, C2, a.codes2))) return r;
+        r = cov_tiles(var, a.codes1, (int)a.cpad1, (int)C1, a.codes2, (int)a.cpad2, (int)C2, fc.W, fc.Minv(), R, fc.noise_c(), fc.scale_c(),
+                      fc.m, fc.bc, wt, symmetric, observation, blocks, fc.caller);
+        if (r) return r;
+        if (mix && (r = cov_accumulate(blocks, C1, C2, a.fm1 + c0 * C1, a.acc1 + C1, a.fm2 + c0 * C2, a.acc2 + C2, wt, wq, fc.bc, c0 == 0,
+                                       mixture_out, fc.caller)))
+            return r;
+        return fc.close_chunk(info_out);
+    });
+    if (rc) return rc;
+    if (mix && (rc = predict_flag(info_out, weights, B, a.flag, fc.caller))) return rc;
+    return cov_finish(mixture_out, C1, C2, a.acc1, a.flag, info_out, weights, B, forest_out, fc.caller);
 }
 
 }  // extern "C"

@@ -28,6 +28,7 @@ from ..forest import _is_torch, _points, packed_forest
 
 MAX_TREES, MAX_LEAVES = 64, 8192  # limits of the leaf-space posterior (include/bark_hip.h)
 MAX_PENDING = 64  # points per call of `condition`, and pending points of a scan
+MAX_COV_POINTS = 65536  # points per side of `covariance`
 
 
 def _align256(n: int) -> int:
@@ -269,6 +270,53 @@ class LeafPosterior:
                 parts.append(self._predict(pts_d, w_d, observation, None, probs[q0:q0 + 16], False, False, chunk, variant)["quantiles"])
             out["quantiles"] = parts[0] if len(parts) == 1 else torch.cat(parts)
         return out if _is_torch(points) else {k: v.cpu().numpy() for k, v in out.items()}
+
+    def covariance(self, x1, x2=None, *, per_forest: bool = False, observation: bool = False, weights=None,
+                   chunk: int | None = None, variant: str = "auto"):
+        """The joint posterior covariance of the weighted mixture of the forests between the points `x1` (C1, d) and `x2`
+        (C2, d), from the state (bark_leaf_posterior_covariance_hip) -> (C1, C2); with `per_forest` the pair (mixture,
+        forest), forest (B, C1, C2) holding every forest's own cov_b(x, x') = (scale_b / m) z(x)' M_b^-1 z(x'), NaN blocks
+        for weight 0.  The mixture is the law of total covariance, sum_b w_b (cov_b + (mu_b - mean)(mu_b - mean)'), with
+        `predict`'s means.  This is the covariance `sample_paths` draws from; `forest_predict(diag=False)` is not.
+
+        x2=None is the symmetric call on x1: only one triangle is computed and the result equals its transpose in bits; its
+        diagonal is `predict`'s variance to rounding.  observation: add every forest's noise s2_b to the diagonal, the
+        covariance of observations at x1; only without x2, because two different evaluations share no noise.  weights,
+        chunk, variant as in `predict`: the state's own importance weights by default, and no result depends on `chunk` or
+        `variant`, bit for bit.  The state is not modified.  At most 65536 points per side.  Torch points give device tensors,
+        numpy points numpy arrays.  Errors as in `scan`; ValueError when an output exceeds the memory budget.  No CPU fallback."""
+        from ..optimizer.acquisition import VARIANTS
+        from .tree_gps import _check_output_budget
+
+        if x2 is not None and observation:
+            raise ValueError("observation=True needs the symmetric call (x2=None): two different evaluations share no noise")
+        x1_d = self._predict_args(x1, variant)
+        if x2 is not None and len(x2) < 1:
+            raise ValueError("a covariance needs at least one point on each side")
+        x2_d = None if x2 is None else _points(x2, self.d)[0]
+        C1 = int(x1_d.shape[0])
+        C2 = C1 if x2_d is None else int(x2_d.shape[0])
+        if max(C1, C2) > MAX_COV_POINTS:
+            raise ValueError(f"covariance takes at most {MAX_COV_POINTS} points per side (got {C1} and {C2})")
+        B, R = self.B, self.R
+        _check_output_budget(8 * C1 * C2 * (B + 1 if per_forest else 1),
+                             f"covariance: {C1} x {C2} points" + (f" for {B} forests" if per_forest else ""))
+
+        import torch
+
+        w_d = self._predict_weights(weights)
+        dev = self.state.device
+        mix = torch.empty((C1, C2), dtype=torch.float64, device=dev)
+        forest = torch.empty((B, C1, C2), dtype=torch.float64, device=dev) if per_forest else None
+        lib = _lib.lib()
+        sym, var = int(x2_d is None), VARIANTS[variant]
+        self._call(lib.bark_leaf_posterior_covariance_hip,
+                   lambda k: int(lib.bark_leaf_posterior_covariance_workspace_bytes(R, self.m, B, k, C1, C2, sym, int(per_forest), 1, var)),
+                   chunk, _lib.ptr(self.state), self.nbytes, _lib.ptr(x1_d), C1, _lib.ptr(x2_d), C2, _lib.ptr(w_d),
+                   int(bool(observation)), var, _lib.ptr(forest), _lib.ptr(mix), weights=w_d)
+        if not (_is_torch(x1) or _is_torch(x2)):
+            mix, forest = mix.cpu().numpy(), None if forest is None else forest.cpu().numpy()
+        return (mix, forest) if per_forest else mix
 
     def scores(self, points, values, *, observation: bool = False, return_values: bool = False, weights=None,
                chunk: int | None = None, variant: str = "auto"):

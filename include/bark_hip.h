@@ -807,6 +807,65 @@ int bark_leaf_posterior_predict_hip(bark_ctx *ctx, const void *packed, const bar
                                     size_t workspace_bytes, int64_t Bc, void *stream);
 
 /* ---------------------------------------------------------------------------------------
+ * Joint covariance from a fitted posterior: the one quantity of the state that is not marginal.  The state of
+ * bark_leaf_posterior_fit_hip, as bark_leaf_posterior_condition_hip / bark_leaf_posterior_observe_hip left it, read at the C1
+ * points x1 (C1, d) and the C2 points x2 (C2, d) (device) under the forest weights w_b: weights (device, (B,), normalised by
+ * the caller) or NULL for 1 / B each.  With z(x) the one-hot leaf row of x (m ones) the posterior covariance of the latent
+ * values at x and x' under forest b is
+ *     cov_b(x, x') = (scale_b / m) z(x)' M_b^-1 z(x')       ( = scale_b K(x, x') - scale_b K(x, X) K_s^-1 scale_b K(X, x') )
+ * the bilinear form of bark_fidelity_gain_fitted_hip's `cov`, for every pair of a C1 x C2 block.  Nothing of size N is read.
+ * Per forest b and pair (i, j), with a_0 < a_1 < ... the leaves of x1[i] and b_0 < b_1 < ... those of x2[j] (code-bit order):
+ *     T_b[i][r]   = sum_k (M_b^-1)[a_k][r]                 k in order, one accumulator from 0.0
+ *     cov_b[i][j] = (scale_b / m) sum_l T_b[i][b_l]        l in order, one accumulator from 0.0, then the one product
+ *   Two stages (part of the contract): m row sums per x1 point, then m gathers per entry, instead of m^2 reads per entry.
+ *   The diagonal of a symmetric call therefore agrees with bark_leaf_posterior_predict_hip's var_bc (which sums the upper
+ *   triangle, dg + 2 off) to rounding, not bit for bit; and cov_b[i][j] agrees with the fidelity gain's `cov` of the same pair to
+ *   rounding (that sum runs over single entries, these over row sums).
+ * Symmetric call, x2 == NULL: x2 = x1 and C2 = C1 (the C2 argument is ignored).  The entries with i >= j are computed by the
+ *   rule above as row i and column j, and entry (j, i) is a copy of entry (i, j): the output is symmetric in bits, and its lower
+ *   triangle has the bits of the general call with x2 = x1.  Only the tiles of that triangle are computed.
+ * observation = 1 (the symmetric call only): s2_b = 1e-6 + noise_b is added to the diagonal of cov_b before anything else uses
+ *   it: the covariance of observations at the points.  Two different evaluations share no noise, so there is no such term
+ *   between x1 and a given x2, even where a row of x2 equals a row of x1.
+ * Outputs (at least one):
+ *   forest_out (B, C1, C2)   cov_b, or NULL.
+ *   mixture_out (C1, C2)     the covariance of the weighted mixture by the law of total covariance in a two-pass form that
+ *                            does not cancel.  mean_i and mean_j are the means of bark_leaf_posterior_predict_hip's recurrence
+ *                            at x1[i] and x2[j] (the same kernel: predict's bits), mu_bi the scan's mu_b(x1[i]), and
+ *                                mixture[i][j] = ( sum_b w_b ( cov_b[i][j] + (mu_bi - mean_i) (mu_bj - mean_j) ) ) / W,  W = sum_b w_b
+ *                            both sums over the forests with w_b != 0 in forest order b = 0 .. B-1 across chunks, from 0.0,
+ *                            every operation as written, rounded once.  With one weight 1.0 and the others 0.0,
+ *                            mixture == cov_b exactly.  Or NULL: then no mean is formed.
+ * Order (part of the contract): as above; no float atomics.  No result depends on Bc or on the variant, bit for bit.
+ * A forest whose weight is exactly 0.0 is skipped whole and its status ignored; its block of forest_out is NaN.  info_out[b]: the
+ *   state's status, or -1 for an invalid categorical value met by a walk of this call.  A non-zero entry of a forest of
+ *   non-zero weight makes every entry of mixture_out NaN and its own block of forest_out NaN; the other blocks are what a call
+ *   without that forest gives.  The state is not modified.  The weights are not read back.
+ * variant: 1 keeps T_b of a workgroup's 32 rows in LDS (32 R doubles beside the leaf lists of its 32 + 64 points) and gathers
+ *   from there; 2 keeps no T and sums every T_b[i][b_l] it needs from M^-1 in global memory, in the same order.  0 takes 1 where
+ *   bark_acquisition_plan does: a table of R (R + 1) / 2 + R doubles that fits a CU's LDS means R <= 200, and then 32 R doubles
+ *   and the lists stay below 64 KiB, so two workgroups share a CU.  One plan for every reader of the state; variant = 1 past
+ *   it is refused.
+ * Limits, refused with BARK_ERR_ARG before any launch (and before the context is looked at): those of the fitted scan (m <= 64,
+ *   R <= 8192, a state buffer of bark_leaf_posterior_bytes aligned to 256, the plan's variant); 1 <= C1, C2 <= 65536 (one slab of
+ *   codes per side); forest_out and mixture_out both NULL; observation other than 0 or 1; observation = 1 with x2 given; x1
+ *   NULL.  Nothing is rerouted.  The call only enqueues: no allocation, no host synchronisation.
+ * workspace >= bark_leaf_posterior_covariance_workspace_bytes(R, m, B, Bc, C1, C2, symmetric, want_forest, want_mixture,
+ *   variant) (pure host code; 0 for a refused shape; symmetric != 0: C2 is ignored): the codes of the C1 + C2 points (C1 when
+ *   symmetric) for Bc forests and a flag word; with want_mixture (4 + 2 B) doubles per point; without want_forest the chunk's
+ *   blocks, Bc C1 C2 doubles.
+ * ------------------------------------------------------------------------------------- */
+size_t bark_leaf_posterior_covariance_workspace_bytes(int64_t max_bits, int64_t m, int64_t B, int64_t Bc, int64_t C1, int64_t C2,
+                                                      int symmetric, int want_forest, int want_mixture, int variant);
+int bark_leaf_posterior_covariance_hip(bark_ctx *ctx, const void *packed, const bark_pack_info *info, int64_t d, const double *noise,
+                                       const double *scale, const void *state, size_t state_bytes, const double *x1 /* (C1, d) */,
+                                       int64_t C1, const double *x2 /* (C2, d) or NULL */, int64_t C2,
+                                       const double *weights /* (B,) or NULL */, int observation, int variant,
+                                       double *forest_out /* (B, C1, C2) or NULL */, double *mixture_out /* (C1, C2) or NULL */,
+                                       int32_t *info_out /* (B,) */, void *workspace, size_t workspace_bytes, int64_t Bc,
+                                       void *stream);
+
+/* ---------------------------------------------------------------------------------------
  * Woodbury / determinant-lemma updates — quick_inverse.py:13-33 (the per-tree step of the sampler,
  * bark_sampler.py:233-257).  With mul = -1 if `subtract` else +1:
  *   K_out         = K_inv - K_inv U (mul I + U' K_inv U)^-1 U' K_inv          (low_rank_inv_update)
